@@ -4,6 +4,13 @@
 np=1/2/4/8").
 
 Run single GPU:    python bench.py --gpus 1 --steps 20 --warmup 5
+    A plain run sets up, warms up, times --steps steps and prints one
+    JSON result line; convolutions run in MIOpen immediate mode on the
+    committed tuning databases (miopen_gfx950/). --full runs the MIOpen
+    exhaustive find instead (minutes). --dump-outputs DIR also writes
+    what the timed step computes (loss and a seeded sample of the
+    updated parameters) as DIR/<name>.npy: the step is run once more
+    after the timed window, from the seeded initial state.
 Run N GPUs (driver):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
@@ -38,7 +45,21 @@ def parse_args():
     ap.add_argument("--bucket-mb", type=int, default=0,
                     help="override the DistributedOptimizer gradient "
                          "bucket size (sets SPARKDL_BUCKET_MB)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last "
+                         "timed step computed as DIR/<name>.npy "
+                         "(float32/float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also do what the headline figure does not "
+                         "need: run the MIOpen exhaustive convolution "
+                         "find (minutes) instead of loading the "
+                         "committed tuning databases")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def log(msg):
@@ -66,8 +87,159 @@ def _load_tunableop():
         log("TunableOp load failed: %s" % (e,))
 
 
+_MIOPEN_DB = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                          "miopen_gfx950")
+
+
+def _load_miopen_tuning(batch=512):
+    """Point MIOpen at the committed find/perf databases for gfx950
+    (captured once from a `--full` run with MIOPEN_USER_DB_PATH set), so
+    immediate mode picks the tuned convolution solvers without paying
+    for the exhaustive find. MIOpen gets a scratch copy: it may rewrite
+    its user databases and the committed files must stay untouched.
+
+    The files are named after one MIOpen build and hold the default
+    ResNet-50 shapes (batch 512, bf16, NHWC) only. Anything else runs
+    untuned immediate mode, which was measured about 9 % slower per
+    step, so that case is logged as a warning and not passed over.
+    Returns the scratch directory, or None if nothing was loaded."""
+    if os.environ.get("MIOPEN_USER_DB_PATH") is not None:
+        return None  # explicit env wins (capture runs)
+    names = []
+    if os.path.isdir(_MIOPEN_DB):
+        names = sorted(f for f in os.listdir(_MIOPEN_DB)
+                       if f.endswith(".txt"))
+    # MIOpen looks its user databases up by <arch>.HIP.<major>_<minor>_
+    # <patch>_<build>...; torch reports the version as one integer
+    ver = torch.backends.cudnn.version() or 0
+    tag = ".HIP.%d_%d_%d_" % (ver // 1000000, ver // 1000 % 1000,
+                              ver % 1000)
+    matching = [f for f in names if tag in f]
+    if not matching:
+        log("WARNING: no committed MIOpen tuning matches this MIOpen "
+            "build (%s): convolutions run untuned immediate mode and the "
+            "figure is not comparable with tuned runs; recapture with "
+            "--full and MIOPEN_USER_DB_PATH" % tag.strip("._"))
+        return None
+    if batch != 512:
+        log("WARNING: the committed MIOpen tuning covers --batch 512 "
+            "only; other shapes run untuned immediate mode (use --full "
+            "for the exhaustive find)")
+    import atexit
+    import shutil
+    import tempfile
+    tmp = tempfile.mkdtemp(prefix="sparkdl_miopen_")
+    atexit.register(shutil.rmtree, tmp, True)
+    for f in matching:
+        shutil.copy(os.path.join(_MIOPEN_DB, f), tmp)
+    os.environ["MIOPEN_USER_DB_PATH"] = tmp
+    log("MIOpen: loaded %d tuning file(s) from %s"
+        % (len(matching), _MIOPEN_DB))
+    return tmp
+
+
+# --dump-outputs budget: a sampled array holds at most this many
+# elements (16 MB as float32, 32 MB as float64), below the 64 MB cap.
+_DUMP_SAMPLE = 4 * 1024 * 1024
+
+
+def _sample_index(n, seed):
+    """Sorted, seeded sample of range(n), or None if n fits the budget."""
+    import numpy as np
+    if n <= _DUMP_SAMPLE:
+        return None
+    idx = np.random.RandomState(seed).choice(n, size=_DUMP_SAMPLE,
+                                             replace=False)
+    idx.sort()
+    return idx
+
+
+def _sampled(tensors, seed):
+    """Flatten `tensors` into one float32 numpy vector, sampled with
+    _sample_index if it is over the budget."""
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+    idx = _sample_index(flat.numel(), seed)
+    if idx is not None:
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.cpu().numpy()
+
+
+class _TrainDump:
+    """--dump-outputs support for a train step.
+
+    The kernels fold partial sums with float atomics, so two runs differ
+    in the last bits of every step, and a training trajectory amplifies
+    that from step to step. To make two runs comparable output for
+    output, the dumped step is the step function run once more, after
+    the timed window, from the seeded initial state: `snapshot()` keeps
+    that state before warmup, `restore()` puts it back in place (same
+    pointers), and `outputs()` is what a caller of the step receives
+    besides the loss: the updated parameters.
+
+    Restored: parameters, buffers, optimizer moments (zero) and fp32
+    masters. Not restored: step counters (`group["step"]`, the AdamW
+    device counter), so with AdamW the bias correction of the dumped
+    step, and with it the dump, depends on --steps and --warmup; with
+    the same arguments it is the same from run to run."""
+
+    def __init__(self, model, opt):
+        self.model, self.opt, self.snap = model, opt, None
+
+    def snapshot(self):
+        self.snap = [t.detach().clone()
+                     for t in self.model.state_dict().values()]
+
+    @torch.no_grad()
+    def restore(self):
+        for t, s in zip(self.model.state_dict().values(), self.snap):
+            t.copy_(s)
+        # optimizer state as at the start: zero moments, fp32 masters
+        # equal to the restored parameters. An optimizer whose state is
+        # not laid out per parameter like this cannot be reset here.
+        state = getattr(self.opt, "state", None)
+        params = [p for p in self.model.parameters() if p.requires_grad]
+        if state is None or any(p not in state for p in params):
+            raise RuntimeError(
+                "--dump-outputs: optimizer %r keeps no per-parameter "
+                "state to reset" % type(self.opt).__name__)
+        for p in params:
+            for k, v in state[p].items():
+                if not torch.is_tensor(v) or v.dim() == 0:
+                    continue  # step counters
+                if v.shape != p.shape:
+                    raise RuntimeError(
+                        "--dump-outputs: unknown optimizer state %r" % k)
+                if k == "master":
+                    v.copy_(p)
+                else:
+                    v.zero_()
+
+    def outputs(self):
+        return {"params": _sampled(list(self.model.parameters()), 0)}
+
+
+def dump_outputs(dirname, arrays):
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype != np.float64:
+            a = a.astype(np.float32)
+        total += a.nbytes
+        assert total <= 64 * 1024 * 1024, "dump exceeds 64 MB"
+        if not np.isfinite(a).all():
+            raise RuntimeError(
+                "--dump-outputs: %s holds %d non-finite values"
+                % (name, int((~np.isfinite(a)).sum())))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log("dumped %s (%d bytes) to %s"
+        % (", ".join(sorted(arrays)), total, dirname))
+
+
 def build_resnet_step(args, device, use_cuda):
-    """Returns (step_fn, items_per_step_per_rank, config_dict)."""
+    """Returns (step_fn, items_per_step_per_rank, config_dict,
+    dump_helper)."""
     from sparkdl.models.resnet import ResNet50
     import sparkdl.ops as ops
 
@@ -105,7 +277,7 @@ def build_resnet_step(args, device, use_cuda):
 
     cfg = {"model": "resnet50", "global_batch": batch * world,
            "seq_len": None, "image": hw, "parallelism": "dp%d" % world}
-    return step, batch, cfg
+    return step, batch, cfg, _TrainDump(model, opt)
 
 
 def build_bert_step(args, device, use_cuda):
@@ -136,7 +308,7 @@ def build_bert_step(args, device, use_cuda):
     step = bert_pretrain_step(model, opt, batch, seq, device, use_cuda)
     cfg = {"model": "bert-base", "global_batch": batch * world,
            "seq_len": seq, "parallelism": "dp%d" % world}
-    return step, batch, cfg
+    return step, batch, cfg, _TrainDump(model, opt)
 
 
 def build_gbt_step(args, device, use_cuda):
@@ -173,7 +345,20 @@ def build_gbt_step(args, device, use_cuda):
 
     cfg = {"model": "gbt", "rows": n, "features": f, "max_depth": 6,
            "parallelism": "single", "global_batch": n, "seq_len": None}
-    return step, 1, cfg
+
+    # same contract as _TrainDump: the dumped round starts from the base
+    # margin with no trees
+    def restore():
+        del booster.trees[:]
+        state["margin"] = margin
+
+    def outputs():
+        m = state["margin"]  # float64, one value per row
+        idx = _sample_index(m.size, 0)
+        return {"margin": m if idx is None else m[idx]}
+
+    return step, 1, cfg, argparse.Namespace(
+        snapshot=lambda: None, restore=restore, outputs=outputs)
 
 
 def main():
@@ -185,10 +370,16 @@ def main():
     if use_cuda:
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         device = torch.device("cuda")
-        # MIOpen exhaustive find (SPARKDL_CONV_FIND=0 disables — immediate
-        # mode keeps rocprof stats free of autotuning noise)
-        torch.backends.cudnn.benchmark = \
-            os.environ.get("SPARKDL_CONV_FIND", "1") == "1"
+        # MIOpen exhaustive find takes minutes and is not needed for the
+        # headline figure once its results are committed: a plain run
+        # uses immediate mode on top of the committed tuning databases,
+        # --full runs the find itself. SPARKDL_CONV_FIND=1/0 forces
+        # either (0 also keeps rocprof stats free of autotuning noise).
+        find = os.environ.get("SPARKDL_CONV_FIND",
+                              "1" if args.full else "0") == "1"
+        torch.backends.cudnn.benchmark = find
+        if not find:
+            _load_miopen_tuning(args.batch)
         _load_tunableop()
     else:
         device = torch.device("cpu")
@@ -230,15 +421,21 @@ def main():
         return
 
     if args.model == "resnet50":
-        step, batch, cfg = build_resnet_step(args, device, use_cuda)
+        step, batch, cfg, dump = build_resnet_step(
+            args, device, use_cuda)
         metric, unit = "images/sec", "images/s"
     elif args.model == "bert":
-        step, batch, cfg = build_bert_step(args, device, use_cuda)
+        step, batch, cfg, dump = build_bert_step(
+            args, device, use_cuda)
         metric, unit = "sequences/sec", "sequences/s"
     else:
         assert world == 1, "gbt bench is single-process"
-        step, batch, cfg = build_gbt_step(args, device, use_cuda)
+        step, batch, cfg, dump = build_gbt_step(
+            args, device, use_cuda)
         metric, unit = "boost_rounds/sec", "rounds/s"
+
+    if args.dump_outputs:
+        dump.snapshot()
 
     for _ in range(args.warmup):
         step()
@@ -251,6 +448,7 @@ def main():
     # overhead hides under compute); keep them for the single-GPU path
     # and run multi-rank eager so the round-end scaling sweep cannot be
     # taken down by a capture-time RCCL deadlock.
+    eager_step = step
     if use_cuda and not args.no_graph and world == 1 \
             and args.model != "gbt":  # gbt steps are host-driven
         try:
@@ -278,7 +476,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     sync()
     elapsed = time.perf_counter() - t0
 
@@ -288,6 +486,20 @@ def main():
         t = torch.tensor([elapsed], device=device if use_cuda else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
+
+    if args.dump_outputs:
+        # the step once more, from the seeded initial state (see
+        # _TrainDump); every rank takes part, rank 0 writes. Where the
+        # timed callable is a captured graph, this extra step is the
+        # same step function run eagerly, not a replay: on MI355X a
+        # replay that follows eager device work (the state reset, or
+        # any kernel writing a fresh allocation) returned non-finite
+        # gradients, and capturing the reset as a graph of its own
+        # ended in a GPU memory fault; the cause of neither is known.
+        dump.restore()
+        sync()
+        last = eager_step()
+        sync()
 
     value = batch * world * args.steps / elapsed
     if rank == 0:
@@ -306,6 +518,13 @@ def main():
             "data": "synthetic",
             "config": cfg,
         }
+        if args.dump_outputs:
+            arrays = dump.outputs()
+            loss = last
+            if torch.is_tensor(loss):
+                arrays["loss"] = loss.detach().float().reshape(1) \
+                    .cpu().numpy()
+            dump_outputs(args.dump_outputs, arrays)
         print(json.dumps(out), flush=True)
 
     if world > 1:

@@ -44,6 +44,34 @@ def test_bench_bert_smoke():
 
 
 @pytest.mark.timeout(600)
+def test_bench_resnet_dump_outputs(tmp_path):
+    """--dump-outputs on the flagship GPU run (graph capture on for the
+    timed steps): the dumped step starts from the seeded initial state,
+    so its loss is that of an untrained 1000-way classifier (ln 1000 =
+    6.908; the seeded init gives 6.928) and the updated parameters stay
+    at their init scale (BN weights are 1)."""
+    import numpy as np
+    d = str(tmp_path / "dump")
+    e = dict(os.environ)
+    out = subprocess.run(
+        [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1",
+         "--steps", "2", "--warmup", "1", "--dump-outputs", d],
+        cwd=REPO, env=e, timeout=420, capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-1500:]
+    assert "hipGraph capture: ON" in out.stdout
+    assert "MIOpen: loaded" in out.stdout
+    rec = json.loads([ln for ln in out.stdout.splitlines()
+                      if ln.startswith("{")][-1])
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+    loss = np.load(os.path.join(d, "loss.npy"))
+    params = np.load(os.path.join(d, "params.npy"))
+    assert loss.dtype == np.float32 and params.dtype == np.float32
+    assert loss.shape == (1,) and 6.85 < float(loss[0]) < 7.0
+    assert params.size == 4 * 1024 * 1024
+    assert np.isfinite(params).all() and np.abs(params).max() < 1.5
+
+
+@pytest.mark.timeout(600)
 def test_bench_gbt_smoke():
     rec = _run_bench(["--model", "gbt", "--steps", "3", "--warmup", "1"],
                      env={"SPARKDL_GBT_ROWS": "400000"})
