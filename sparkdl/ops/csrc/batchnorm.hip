@@ -4,13 +4,40 @@
 //
 // channels_last [N,C,H,W] tensors are exactly [rows=N*H*W, C] row-major,
 // so the channel dim is the contiguous innermost axis. All kernels use
-// short8 (16 B/lane) vector access; per-channel reductions accumulate in
-// registers over grid-strided rows and fold with ONE global atomic per
-// thread (Guideline 12).
+// short8 (16 B/lane) vector access.
+//
+// Per-channel reductions (batch statistics, dgamma/dbeta) run in two
+// stages with no float atomics anywhere (Guideline 12, partial-slab
+// reducer), so they are bitwise reproducible from run to run:
+//   1. bn_stats_k / bn_bwd_reduce_k: G blocks grid-stride over the rows,
+//      kUnroll rows of independent 16 B loads in flight per thread,
+//      accumulating in registers. Each block folds its threads' partials
+//      in a fixed order (bn_block_fold) and writes its 2*C sums with
+//      plain vector stores to its own row of an fp32 slab [G][2*C].
+//      Every one of the G rows is written in every call, so the slab is
+//      neither zeroed nor reused across calls.
+//   2. bn_finalize_k / bn_bwd_finalize_k: 64 threads per channel sum the
+//      G slab rows in a fixed order, then compute the per-channel
+//      statistics and coefficients.
+//
+// Reduce grid G (bn_reduce_blocks), chosen per site:
+//   G = min(row_blocks, max(256, min(512, rows / 64)))
+//   - row_blocks = ceil(rows / rows-per-block): never a block without
+//     rows.
+//   - rows / 64: a block sums at least 64 rows, so slab write plus
+//     read-back (16*G*C bytes) is at most 1/8 of the bf16 input
+//     (2*rows*C bytes); at the batch-512 ResNet-50 sites it is
+//     0.06-12.5 %.
+//   - cap 512: two blocks per CU with kUnroll rows of loads per thread
+//     already stream at 5.2-6.7 TB/s at the batch-512 ResNet-50 sites
+//     (profiles/bn_microbench.txt); 768-2048 blocks are within a few
+//     percent either way and only add slab rows to write and read back.
+//   - floor 256: one block per CU. Sites this small are latency-bound,
+//     and the slab there is at most 256 rows (<= 4 MB at C=2048).
 //
 // Replaces the MIOpen BN + eager ReLU + eager residual-add chain (and
 // their autocast fp32 round-trips) with:
-//   fwd: stats (1 pass over x) -> finalize (C threads) -> apply (1 pass)
+//   fwd: stats (1 pass over x) -> finalize -> apply (1 pass)
 //   bwd: reduce (1 pass) -> finalize -> apply (1 pass)
 // vs MIOpen's separate BN fwd/bwd + ReLU fwd/bwd + add kernels.
 
@@ -21,40 +48,127 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kVec = 8;
+// Rows of independent loads in flight per thread in the reduce loops.
+// Measured at the ResNet-50 sites: 2 beats 1 by up to 35 % at G <= 512;
+// 4 gains nothing in bn_stats_k and loses in bn_bwd_reduce_k.
+constexpr int kUnroll = 2;
+// Block-fold tile: rows-per-block * 2*C floats <= 256 threads * 16.
+constexpr int kFoldFloats = kBlock * 2 * kVec;  // 16 KB
+// Second stage: each block finalizes kFinCh channels with
+// kBlock / kFinCh = 64 slab-row lanes per channel.
+constexpr int kFinCh = 4;
 
 // --------------------------------------------------------------------
 // Forward
 // --------------------------------------------------------------------
 
-// Fold a per-thread [kVec] accumulator pair into the block's LDS tile
-// (one slot per column), then ONE global atomic per column per block —
-// without this, 2048 blocks x 256 threads of same-address global
-// atomics serialize on small-C layers (Guideline 12).
+// Store an accumulator pair as 16 B vectors: a at p[0..8), b at
+// p[cols..cols+8).
+__device__ __forceinline__ void bn_store_pair(
+    float* p, int cols, const float (&a)[kVec], const float (&b)[kVec]) {
+  *(float4v*)(p) = float4v{a[0], a[1], a[2], a[3]};
+  *(float4v*)(p + 4) = float4v{a[4], a[5], a[6], a[7]};
+  *(float4v*)(p + cols) = float4v{b[0], b[1], b[2], b[3]};
+  *(float4v*)(p + cols + 4) = float4v{b[4], b[5], b[6], b[7]};
+}
+
+// Fold the per-thread [kVec] accumulator pairs of a block into one
+// [2*cols] row and store it to the block's slab row. Threads that hold
+// the same columns sit `tpr` apart; their partials go to an LDS tile
+// [rpb][2*cols] and are summed by a halving tree over the row index
+// (rows [s, n) add into rows [0, n-s)), which fixes the order of every
+// addition for any rpb, power of two or not. Row 0 ends with the block
+// total in registers. Called by all kBlock threads.
 __device__ __forceinline__ void bn_block_fold(
-    float* lds_a, float* lds_b, const float* a, const float* b,
-    int lane_col, int cols, float* out_a, float* out_b) {
-  for (int c = threadIdx.x; c < cols; c += kBlock) {
-    lds_a[c] = 0.f;
-    lds_b[c] = 0.f;
-  }
-  __syncthreads();
+    float* lds, float (&a)[kVec], float (&b)[kVec], int rpb, int row_off,
+    int lane_col, int cols, float* __restrict__ slab_row) {
+  const bool active = row_off < rpb;
+  // only dereferenced by active threads: row_off < rpb keeps it in-tile
+  float* mine = lds + (size_t)row_off * 2 * cols + lane_col;
+  if (active) bn_store_pair(mine, cols, a, b);
+  int s = 1;
+  while (s < rpb) s <<= 1;
+  int n = rpb;  // live rows
+  for (s >>= 1; s >= 1; s >>= 1) {
+    __syncthreads();
+    if (row_off < s && row_off + s < n) {
+      const float* peer = mine + (size_t)s * 2 * cols;
+      const float4v pa0 = *(const float4v*)(peer);
+      const float4v pa1 = *(const float4v*)(peer + 4);
+      const float4v pb0 = *(const float4v*)(peer + cols);
+      const float4v pb1 = *(const float4v*)(peer + cols + 4);
 #pragma unroll
-  for (int j = 0; j < kVec; ++j) {
-    atomicAdd(&lds_a[lane_col + j], a[j]);  // LDS atomics: per-CU, cheap
-    atomicAdd(&lds_b[lane_col + j], b[j]);
+      for (int j = 0; j < 4; ++j) {
+        a[j] += pa0[j];
+        a[j + 4] += pa1[j];
+        b[j] += pb0[j];
+        b[j + 4] += pb1[j];
+      }
+      // rows [0, s) are read again at the next step
+      if (s > 1) bn_store_pair(mine, cols, a, b);
+    }
+    n = min(n, s);
+  }
+  if (row_off == 0) bn_store_pair(slab_row + lane_col, cols, a, b);
+}
+
+// Second stage: sum column c and column cols+c of the G slab rows for
+// the block's kFinCh channels. Thread t takes channel t % kFinCh and
+// slab rows t / kFinCh, +64, ...; the 16 row lanes of a wave fold by
+// butterfly, the 4 waves through LDS, all in a fixed order. Threads
+// 0..kFinCh-1 return the totals of channel blk*kFinCh + t.
+__device__ __forceinline__ void bn_slab_sum(
+    const float* __restrict__ slab, int G, int cols, int blk, float* red,
+    float& sum_a, float& sum_b) {
+  const int c = blk * kFinCh + threadIdx.x % kFinCh;
+  float sa = 0.f, sb = 0.f;
+#pragma unroll 4
+  for (int g = threadIdx.x / kFinCh; g < G; g += kBlock / kFinCh) {
+    const float* row = slab + (size_t)g * 2 * cols;
+    sa += row[c];
+    sb += row[cols + c];
+  }
+#pragma unroll
+  for (int off = kFinCh; off < WAVE; off <<= 1) {
+    sa += __shfl_xor(sa, off, WAVE);
+    sb += __shfl_xor(sb, off, WAVE);
+  }
+  const int lane = threadIdx.x % WAVE;
+  const int wid = threadIdx.x / WAVE;
+  if (lane < kFinCh) {
+    red[wid * 2 * kFinCh + lane] = sa;
+    red[wid * 2 * kFinCh + kFinCh + lane] = sb;
   }
   __syncthreads();
-  for (int c = threadIdx.x; c < cols; c += kBlock) {
-    atomicAdd(&out_a[c], lds_a[c]);
-    atomicAdd(&out_b[c], lds_b[c]);
+  sum_a = 0.f;
+  sum_b = 0.f;
+  if (threadIdx.x < kFinCh) {
+#pragma unroll
+    for (int w = 0; w < kBlock / WAVE; ++w) {
+      sum_a += red[w * 2 * kFinCh + threadIdx.x];
+      sum_b += red[w * 2 * kFinCh + kFinCh + threadIdx.x];
+    }
   }
 }
 
-// scratch layout: [0..C) sum, [C..2C) sumsq  (pre-zeroed)
+// Channel group of a finalize block. Consecutive blocks are dealt
+// round-robin to the 8 XCDs, whose L2s are separate; with 16 B of a
+// 128 B slab line per block, eight neighbours would pull every line
+// into eight L2s (measured at C=2048, G=392: 11.4 us against 5.2). Giving
+// each XCD one contiguous channel range fetches a line once. Only a
+// placement hint: any mapping is correct as long as it is a bijection.
+__device__ __forceinline__ int bn_fin_block() {
+  const int nb = gridDim.x;
+  if (nb % 8) return blockIdx.x;
+  return (blockIdx.x % 8) * (nb / 8) + blockIdx.x / 8;
+}
+
+// slab row layout: [0..C) sum, [C..2C) sumsq
+template <int U>
 __global__ __launch_bounds__(kBlock) void bn_stats_k(
-    const short* __restrict__ x, float* __restrict__ scratch,
+    const short* __restrict__ x, float* __restrict__ slab,
     long long rows, int cols) {
-  __shared__ float lds[2 * 2048];
+  __shared__ __attribute__((aligned(16))) float lds[kFoldFloats];
   const int tpr = cols / kVec;             // threads per row (cols%8==0)
   const int rpb = kBlock / min(tpr, kBlock);
   const int lane_col = (threadIdx.x % tpr) * kVec;
@@ -62,8 +176,25 @@ __global__ __launch_bounds__(kBlock) void bn_stats_k(
 
   float s[kVec] = {0.f}, ss[kVec] = {0.f};
   if (row_off < rpb) {
-    for (long long r = (long long)blockIdx.x * rpb + row_off; r < rows;
-         r += (long long)gridDim.x * rpb) {
+    const long long stride = (long long)gridDim.x * rpb;
+    long long r = (long long)blockIdx.x * rpb + row_off;
+    // U rows of loads issued before the first use
+    for (; r + (U - 1) * stride < rows; r += U * stride) {
+      short8 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        v[u] = *(const short8*)(x + (r + u * stride) * cols + lane_col);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) {
+          const float f = bf2f(v[u][j]);
+          s[j] += f;
+          ss[j] += f * f;
+        }
+      }
+    }
+    for (; r < rows; r += stride) {
       const short8 v = *(const short8*)(x + r * cols + lane_col);
 #pragma unroll
       for (int j = 0; j < kVec; ++j) {
@@ -73,25 +204,30 @@ __global__ __launch_bounds__(kBlock) void bn_stats_k(
       }
     }
   }
-  bn_block_fold(lds, lds + cols, s, ss, lane_col, cols, scratch,
-                scratch + cols);
+  bn_block_fold(lds, s, ss, rpb, row_off, lane_col, cols,
+                slab + (size_t)blockIdx.x * 2 * cols);
 }
 
-// One thread per channel: batch stats, running-stat update, and the
-// fused apply coefficients scale=gamma*rstd, shift=beta-mean*scale.
-__global__ void bn_finalize_k(
-    const float* __restrict__ scratch, const float* __restrict__ gamma,
+// Second stage of the statistics (grid = cols / kFinCh blocks): sum the
+// G slab rows per channel, then batch stats, running-stat update, and
+// the fused apply coefficients scale=gamma*rstd, shift=beta-mean*scale.
+__global__ __launch_bounds__(kBlock) void bn_finalize_k(
+    const float* __restrict__ slab, int G, const float* __restrict__ gamma,
     const float* __restrict__ beta, float* __restrict__ running_mean,
     float* __restrict__ running_var, float* __restrict__ save_mean,
     float* __restrict__ save_rstd, float* __restrict__ scale,
     float* __restrict__ shift, long long rows, int cols, float momentum,
     float eps, int training) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
+  __shared__ float red[kBlock / WAVE * 2 * kFinCh];
+  float sum = 0.f, sumsq = 0.f;
+  const int blk = bn_fin_block();
+  if (training) bn_slab_sum(slab, G, cols, blk, red, sum, sumsq);  // uniform
+  if (threadIdx.x >= kFinCh) return;
+  const int c = blk * kFinCh + threadIdx.x;
   float mean, rstd;
   if (training) {
-    mean = scratch[c] / rows;
-    const float var = fmaxf(scratch[cols + c] / rows - mean * mean, 0.f);
+    mean = sum / rows;
+    const float var = fmaxf(sumsq / rows - mean * mean, 0.f);
     rstd = rsqrtf(var + eps);
     // torch semantics: running_var tracks the UNBIASED batch variance.
     const float unbiased = rows > 1 ? var * rows / (rows - 1) : var;
@@ -155,15 +291,15 @@ __global__ __launch_bounds__(kBlock) void bn_apply_k(
 // Backward
 // --------------------------------------------------------------------
 // dym = dy * relu_mask (mask from saved output y > 0).
-// scratch: [0..C) sum(dym), [C..2C) sum(dym * xhat)   (pre-zeroed)
+// slab row layout: [0..C) sum(dym), [C..2C) sum(dym * xhat)
 
-template <bool RELU>
+template <bool RELU, int U>
 __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_k(
     const short* __restrict__ x, const unsigned char* __restrict__ mask,
     const short* __restrict__ dy, const float* __restrict__ save_mean,
-    const float* __restrict__ save_rstd, float* __restrict__ scratch,
+    const float* __restrict__ save_rstd, float* __restrict__ slab,
     long long rows, int cols) {
-  __shared__ float lds[2 * 2048];
+  __shared__ __attribute__((aligned(16))) float lds[kFoldFloats];
   const int tpr = cols / kVec;
   const int rpb = kBlock / min(tpr, kBlock);
   const int lane_col = (threadIdx.x % tpr) * kVec;
@@ -175,13 +311,8 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_k(
     const float4v m1 = *(const float4v*)(save_mean + lane_col + 4);
     const float4v r0 = *(const float4v*)(save_rstd + lane_col);
     const float4v r1 = *(const float4v*)(save_rstd + lane_col + 4);
-    for (long long r = (long long)blockIdx.x * rpb + row_off; r < rows;
-         r += (long long)gridDim.x * rpb) {
-      const long long base = r * cols + lane_col;
-      const short8 xv = *(const short8*)(x + base);
-      const short8 dv = *(const short8*)(dy + base);
-      unsigned char mbits = 0xffu;
-      if (RELU) mbits = mask[base / kVec];
+    auto accum = [&](const short8& xv, const short8& dv,
+                     unsigned char mbits) {
 #pragma unroll
       for (int j = 0; j < kVec; ++j) {
         float d = bf2f(dv[j]);
@@ -192,23 +323,51 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_k(
         s1[j] += d;
         s2[j] += d * xh;
       }
+    };
+    const long long stride = (long long)gridDim.x * rpb;
+    long long r = (long long)blockIdx.x * rpb + row_off;
+    // U rows of loads issued before the first use
+    for (; r + (U - 1) * stride < rows; r += U * stride) {
+      short8 xv[U], dv[U];
+      unsigned char mb[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long long base = (r + u * stride) * cols + lane_col;
+        xv[u] = *(const short8*)(x + base);
+        dv[u] = *(const short8*)(dy + base);
+        mb[u] = 0xffu;
+        if (RELU) mb[u] = mask[base / kVec];
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) accum(xv[u], dv[u], mb[u]);
+    }
+    for (; r < rows; r += stride) {
+      const long long base = r * cols + lane_col;
+      const short8 xv = *(const short8*)(x + base);
+      const short8 dv = *(const short8*)(dy + base);
+      unsigned char mbits = 0xffu;
+      if (RELU) mbits = mask[base / kVec];
+      accum(xv, dv, mbits);
     }
   }
-  bn_block_fold(lds, lds + cols, s1, s2, lane_col, cols, scratch,
-                scratch + cols);
+  bn_block_fold(lds, s1, s2, rpb, row_off, lane_col, cols,
+                slab + (size_t)blockIdx.x * 2 * cols);
 }
 
+// Second stage of the backward reduction (grid = cols / kFinCh blocks):
 // dgamma = sum(dym*xhat), dbeta = sum(dym); coefficients for the apply.
-__global__ void bn_bwd_finalize_k(
-    const float* __restrict__ scratch, const float* __restrict__ gamma,
+__global__ __launch_bounds__(kBlock) void bn_bwd_finalize_k(
+    const float* __restrict__ slab, int G, const float* __restrict__ gamma,
     const float* __restrict__ save_rstd, float* __restrict__ dgamma,
     float* __restrict__ dbeta, float* __restrict__ c1,
     float* __restrict__ c2, float* __restrict__ c3, long long rows,
     int cols, int training) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
-  const float sum_dym = scratch[c];
-  const float sum_dymxh = scratch[cols + c];
+  __shared__ float red[kBlock / WAVE * 2 * kFinCh];
+  float sum_dym, sum_dymxh;
+  const int blk = bn_fin_block();
+  bn_slab_sum(slab, G, cols, blk, red, sum_dym, sum_dymxh);
+  if (threadIdx.x >= kFinCh) return;
+  const int c = blk * kFinCh + threadIdx.x;
   dgamma[c] = sum_dymxh;
   dbeta[c] = sum_dym;
   c1[c] = gamma[c] * save_rstd[c];
@@ -281,6 +440,19 @@ int bn_grid(long long rows, int cols) {
 
 }  // namespace
 
+// Reduce grid = slab rows; the rule is derived in the header comment.
+int bn_reduce_blocks(long long rows, int cols) {
+  const int tpr = cols / kVec;
+  const int rpb = kBlock / min(tpr, kBlock);
+  const long long row_blocks = (rows + rpb - 1) / rpb;
+  const long long g = max(256LL, min(512LL, rows / 64));
+  return (int)max(1LL, min(row_blocks, g));
+}
+
+long long bn_scratch_floats(long long rows, int cols) {
+  return (long long)bn_reduce_blocks(rows, cols) * 2 * cols + 3LL * cols;
+}
+
 void launch_bn_fwd(const short* x, const short* res, const float* gamma,
                    const float* beta, float* running_mean,
                    float* running_var, float* save_mean, float* save_rstd,
@@ -288,14 +460,15 @@ void launch_bn_fwd(const short* x, const short* res, const float* gamma,
                    long long rows, int cols, float momentum, float eps,
                    bool training, bool relu, hipStream_t stream) {
   const int grid = bn_grid(rows, cols);
+  const int G = bn_reduce_blocks(rows, cols);
   if (training)
-    hipLaunchKernelGGL(bn_stats_k, dim3(grid), dim3(kBlock), 0, stream, x,
-                       scratch, rows, cols);
-  // scale/shift reuse scratch[2C..4C)
-  float* scale = scratch + 2 * cols;
-  float* shift = scratch + 3 * cols;
-  hipLaunchKernelGGL(bn_finalize_k, dim3((cols + 255) / 256), dim3(256), 0,
-                     stream, scratch, gamma, beta, running_mean,
+    hipLaunchKernelGGL(bn_stats_k<kUnroll>, dim3(G), dim3(kBlock), 0,
+                       stream, x, scratch, rows, cols);
+  // scratch: slab [G][2C], then scale [C], shift [C]
+  float* scale = scratch + (size_t)G * 2 * cols;
+  float* shift = scale + cols;
+  hipLaunchKernelGGL(bn_finalize_k, dim3(cols / kFinCh), dim3(kBlock), 0,
+                     stream, scratch, G, gamma, beta, running_mean,
                      running_var, save_mean, save_rstd, scale, shift, rows,
                      cols, momentum, eps, (int)training);
   auto ap = relu ? (res ? bn_apply_k<true, true> : bn_apply_k<true, false>)
@@ -312,14 +485,17 @@ void launch_bn_bwd(const short* x, const unsigned char* mask,
                    short* dres, long long rows, int cols, bool training,
                    bool relu, hipStream_t stream) {
   const int grid = bn_grid(rows, cols);
-  auto rk = relu ? bn_bwd_reduce_k<true> : bn_bwd_reduce_k<false>;
-  hipLaunchKernelGGL(rk, dim3(grid), dim3(kBlock), 0, stream, x, mask, dy,
+  const int G = bn_reduce_blocks(rows, cols);
+  auto rk = relu ? bn_bwd_reduce_k<true, kUnroll>
+                 : bn_bwd_reduce_k<false, kUnroll>;
+  hipLaunchKernelGGL(rk, dim3(G), dim3(kBlock), 0, stream, x, mask, dy,
                      save_mean, save_rstd, scratch, rows, cols);
-  float* c1 = scratch + 2 * cols;
-  float* c2 = scratch + 3 * cols;
-  float* c3 = scratch + 4 * cols;
-  hipLaunchKernelGGL(bn_bwd_finalize_k, dim3((cols + 255) / 256), dim3(256),
-                     0, stream, scratch, gamma, save_rstd, dgamma, dbeta,
+  // scratch: slab [G][2C], then c1, c2, c3 [C] each
+  float* c1 = scratch + (size_t)G * 2 * cols;
+  float* c2 = c1 + cols;
+  float* c3 = c2 + cols;
+  hipLaunchKernelGGL(bn_bwd_finalize_k, dim3(cols / kFinCh), dim3(kBlock),
+                     0, stream, scratch, G, gamma, save_rstd, dgamma, dbeta,
                      c1, c2, c3, rows, cols, (int)training);
   auto ak = relu ? (dres ? bn_bwd_apply_k<true, true>
                          : bn_bwd_apply_k<true, false>)

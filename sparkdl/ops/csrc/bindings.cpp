@@ -175,7 +175,8 @@ std::vector<at::Tensor> bn_fwd(const at::Tensor& x,
   auto y = at::empty_like(x);
   auto save_mean = at::empty({cols}, f32);
   auto save_rstd = at::empty({cols}, f32);
-  auto scratch = at::zeros({5 * cols}, f32);
+  // partial-sum slab + coefficients; fully written before it is read
+  auto scratch = at::empty({bn_scratch_floats(rows, cols)}, f32);
   at::Tensor mask;
   unsigned char* mask_ptr = nullptr;
   if (relu) {
@@ -213,7 +214,7 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& x,
   auto dx = at::empty_like(x);
   auto dgamma = at::empty({cols}, f32);
   auto dbeta = at::empty({cols}, f32);
-  auto scratch = at::zeros({5 * cols}, f32);
+  auto scratch = at::empty({bn_scratch_floats(rows, cols)}, f32);
   at::Tensor dres;
   short* dres_ptr = nullptr;
   if (needs_dres) {

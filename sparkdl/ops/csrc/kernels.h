@@ -66,9 +66,14 @@ void launch_bias_gelu_bwd(const short* x, const float* bias,
                           long long rows, int cols, hipStream_t stream);
 
 // Fused BatchNorm(+residual)(+ReLU), bf16 NHWC, fp32 stats
-// (SURVEY.md §2.2 N4/N5). scratch: fp32[5*cols], pre-zeroed [0..2C).
-// With relu, the forward packs the activation mask 1 bit/elem
-// (uint8[rows*cols/8]) so backward never re-reads y.
+// (SURVEY.md §2.2 N4/N5). scratch: fp32[bn_scratch_floats(rows, cols)],
+// uninitialized: a partial-sum slab [bn_reduce_blocks][2*cols] that the
+// reduce kernel fully writes in each call, then the per-channel
+// coefficients. With relu, the forward packs the activation mask
+// 1 bit/elem (uint8[rows*cols/8]) so backward never re-reads y.
+int bn_reduce_blocks(long long rows, int cols);
+long long bn_scratch_floats(long long rows, int cols);
+
 void launch_bn_fwd(const short* x, const short* res, const float* gamma,
                    const float* beta, float* running_mean,
                    float* running_var, float* save_mean, float* save_rstd,
