@@ -59,7 +59,11 @@ class BertSelfAttention(nn.Module):
         self.out = Linear(cfg.hidden, cfg.hidden)
         self.drop_p = cfg.dropout
 
-    def forward(self, x):
+    def forward(self, x, seq_lens=None):
+        """seq_lens: optional int32 [B] on x's device — valid length of
+        each right-padded row. Padded keys are never attended to and
+        the attention output at padded positions is exactly zero, on
+        the flash path and on the fallback path alike."""
         from sparkdl.ops import functional as F_
         B, S, H = x.shape
         qkv = self.qkv(x).view(B, S, 3, self.heads, self.head_dim)
@@ -69,12 +73,19 @@ class BertSelfAttention(nn.Module):
             # hand-written CDNA4 flash kernels (fwd+bwd, in-kernel
             # dropout), reading the packed qkv buffer with strided rows
             # and writing O as [B,S,H] directly — no Triton and no
-            # permute/contiguous copies on the hot path
-            o = F_.flash_attention_packed(qkv, dropout_p=p)
+            # permute/contiguous copies on the hot path; lengths are
+            # read in-kernel (padded tiles skipped, no host sync)
+            o = F_.flash_attention_packed(qkv, dropout_p=p,
+                                          seq_lens=seq_lens)
         else:
             q, k, v = qkv.permute(2, 0, 3, 1, 4).unbind(0)  # [B,h,S,d]
-            o = nn.functional.scaled_dot_product_attention(
-                q, k, v, dropout_p=p)
+            if seq_lens is None:
+                o = nn.functional.scaled_dot_product_attention(
+                    q, k, v, dropout_p=p)
+            else:
+                # same semantics as the kernels (zero padded rows)
+                o = F_.masked_attention_ref(q, k, v, seq_lens,
+                                            dropout_p=p)
             o = o.transpose(1, 2).reshape(B, S, H)
         return self.out(o)
 
@@ -89,8 +100,8 @@ class BertLayer(nn.Module):
         self.ln2 = LayerNorm(cfg.hidden, eps=1e-12)
         self.drop = nn.Dropout(cfg.dropout)
 
-    def forward(self, x):
-        x = self.ln1(x + self.drop(self.attn(x)))
+    def forward(self, x, seq_lens=None):
+        x = self.ln1(x + self.drop(self.attn(x, seq_lens)))
         x = self.ln2(x + self.drop(self.ffn_out(self.ffn_in(x))))
         return x
 
@@ -116,7 +127,35 @@ class BertBase(nn.Module):
         elif isinstance(m, nn.Embedding):
             nn.init.normal_(m.weight, std=0.02)
 
-    def encode(self, ids, token_type=None):
+    @staticmethod
+    def _seq_lens(ids, attention_mask, seq_lens):
+        """Resolve the padding arguments to int32 [B] lengths on ids'
+        device (or None), once per forward."""
+        if attention_mask is not None and seq_lens is not None:
+            raise ValueError(
+                "pass either attention_mask or seq_lens, not both")
+        if attention_mask is not None:
+            from sparkdl.ops.functional import seqlens_from_mask
+            if attention_mask.shape != ids.shape:
+                raise ValueError("attention_mask must match ids' [B, S]")
+            seq_lens = seqlens_from_mask(attention_mask.to(ids.device))
+        if seq_lens is None:
+            return None
+        return torch.as_tensor(seq_lens).to(
+            device=ids.device, dtype=torch.int32).contiguous()
+
+    def encode(self, ids, token_type=None, *, attention_mask=None,
+               seq_lens=None):
+        """Hidden states [B, S, hidden].
+
+        Variable-length batches are right-padded: pass either
+        ``attention_mask`` ([B,S], 1 = token, each row a prefix of
+        ones; validated, which syncs once outside graph capture) or
+        ``seq_lens`` (int [B]; the sync-free path). Padded keys are
+        then never attended to, so hidden states at valid positions do
+        not depend on the padding. Hidden states AT padded positions
+        are unspecified but finite."""
+        seq_lens = self._seq_lens(ids, attention_mask, seq_lens)
         h = self.embeddings(ids, token_type)
         # Keep the residual stream in the autocast compute dtype (bf16) so
         # every LayerNorm / bias+GELU hits the CDNA4 kernels; embeddings
@@ -124,7 +163,7 @@ class BertBase(nn.Module):
         if h.is_cuda and torch.is_autocast_enabled():
             h = h.to(torch.get_autocast_dtype("cuda"))
         for layer in self.encoder:
-            h = layer(h)
+            h = layer(h, seq_lens)
         return h
 
     def _mlm_logits(self, h):
@@ -133,30 +172,51 @@ class BertBase(nn.Module):
             h, self.embeddings.word.weight.to(h.dtype), None)
         return logits + self.mlm_bias.to(logits.dtype)
 
-    def forward(self, ids, token_type=None):
-        return self._mlm_logits(self.encode(ids, token_type))
+    def forward(self, ids, token_type=None, *, attention_mask=None,
+                seq_lens=None):
+        """MLM logits [B, S, vocab]; padding arguments as in encode()
+        (logits at padded positions are unspecified but finite)."""
+        return self._mlm_logits(self.encode(
+            ids, token_type, attention_mask=attention_mask,
+            seq_lens=seq_lens))
 
-    def forward_mlm(self, ids, positions, token_type=None):
+    def forward_mlm(self, ids, positions, token_type=None, *,
+                    attention_mask=None, seq_lens=None):
         """MLM logits only at the masked positions (flat indices into the
         [B*S] token stream) — the vocab projection runs on ~15% of tokens
-        instead of all of them, the standard pretrain-head optimization."""
-        h = self.encode(ids, token_type)
+        instead of all of them, the standard pretrain-head optimization.
+        Padding arguments as in encode()."""
+        h = self.encode(ids, token_type, attention_mask=attention_mask,
+                        seq_lens=seq_lens)
         h = h.reshape(-1, self.cfg.hidden).index_select(0, positions)
         return self._mlm_logits(h)
 
 
 def bert_pretrain_step(model, opt, batch, seq, device, use_cuda,
-                       mask_frac=0.15):
+                       mask_frac=0.15, seq_lens=None):
     """Build a closure running one synthetic MLM pretrain step.
 
     The vocab projection + loss run only on the masked positions
     (mask_frac of tokens), as in real MLM pretraining.
+
+    seq_lens (optional, int [batch]): treat the batch as right-padded
+    to ``seq`` with these valid lengths — MLM positions are drawn only
+    among valid tokens and the lengths go to the model (device-side,
+    no per-step host sync).
     """
     cfg = model.cfg
     g = torch.Generator(device="cpu").manual_seed(7)
     ids = torch.randint(0, cfg.vocab_size, (batch, seq), generator=g) \
         .to(device)
     mask = torch.rand(batch, seq, generator=g) < mask_frac
+    lens_dev = None
+    if seq_lens is not None:
+        lens = torch.as_tensor(seq_lens).to("cpu", torch.int64) \
+            .clamp(0, seq)
+        if lens.shape != (batch,):
+            raise ValueError("seq_lens must hold one length per row")
+        mask &= torch.arange(seq).unsqueeze(0) < lens.unsqueeze(1)
+        lens_dev = lens.to(device=device, dtype=torch.int32)
     positions = mask.flatten().nonzero(as_tuple=False).flatten().to(device)
     labels = ids.flatten().index_select(0, positions)
     autocast_dev = "cuda" if use_cuda else "cpu"
@@ -167,12 +227,14 @@ def bert_pretrain_step(model, opt, batch, seq, device, use_cuda,
     def step():
         opt.zero_grad()
         if pure_bf16:
-            logits = model.forward_mlm(ids, positions)
+            logits = model.forward_mlm(ids, positions,
+                                       seq_lens=lens_dev)
             loss = torch.nn.functional.cross_entropy(
                 logits.float(), labels)
         else:
             with torch.autocast(autocast_dev, dtype=torch.bfloat16):
-                logits = model.forward_mlm(ids, positions)
+                logits = model.forward_mlm(ids, positions,
+                                           seq_lens=lens_dev)
                 loss = torch.nn.functional.cross_entropy(
                     logits.float(), labels)
         loss.backward()

@@ -40,6 +40,8 @@ def has_ext():
 
 from sparkdl.ops.functional import (  # noqa: F401,E402
     layer_norm, bias_gelu, batch_norm_act, layer_norm_ref, bias_gelu_ref,
+    flash_attention, flash_attention_packed, masked_attention_ref,
+    seqlens_from_mask,
 )
 from sparkdl.ops.modules import (  # noqa: F401,E402
     LayerNorm, Linear, LinearGelu, Conv1x1, BatchNormAct2d,

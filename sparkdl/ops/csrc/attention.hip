@@ -35,6 +35,27 @@
 // regenerated identically in forward and backward; the seed lives in
 // DEVICE memory so the op is hipGraph-capture safe.
 //
+// Variable-length batches (template <bool VARLEN>, chosen by a non-null
+// `seqlens`): rows are right-padded, seqlens[bh / H] (DEVICE int32,
+// clamped into [0,S]) is the number of valid tokens. Only keys < len
+// are attended to; query rows >= len give exactly zero O and dQ and
+// feed nothing into dK/dV; dK/dV rows >= len are exactly zero.
+//   * A block whose whole tile is padding stores a zero tile (fwd: and
+//     LSE = 0) and returns — a block-uniform branch taken before any
+//     barrier or global_load_lds. The others loop over ceil(len/64)
+//     tiles instead of S/64, so a padded row costs ~len^2, not S^2.
+//   * In the tail tile, padded keys are taken out of the running max
+//     and get p = 0 by SELECTION (cond ? x : 0, never x * 0: LSE/Drow
+//     of padded rows may hold anything). Every processed tile holds at
+//     least one valid key, so the running max stays finite.
+//   * Tail-tile staging and the pre-transposes still cover full tiles
+//     (in bounds: S % 64 == 0). A zero P does not shield an MFMA from
+//     a non-finite operand, so padded rows must hold FINITE values.
+//   * Dropout keeps hashing (seed, bh, q*S+k): a valid (q,k) pair gets
+//     the decision of the unmasked call with the same seed.
+// The VARLEN=false instantiations are the fixed-length kernels,
+// instruction for instruction.
+//
 // LDS tiles are [row][64] bf16 with the st_16x32 XOR swizzle on both
 // sides (pre-permuted global_load_lds sources + swizzled ds accesses):
 // without it the 16-lane column reads are 16-way bank conflicts.
@@ -111,6 +132,24 @@ __device__ __forceinline__ void stage_tile(short* dst, const short* g,
   }
 }
 
+// Variable-length batches (VARLEN): a block whose whole tile lies in the
+// padding stores a zero [64][64] tile (rows `stride` elements apart) and
+// returns. 256 threads x 2 x 16 B.
+__device__ __forceinline__ void zero_tile(short* g, long long stride,
+                                          int tid) {
+  const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+  short* p = g + (long long)(tid / 4) * stride + (tid % 4) * 16;
+  *(bf16x8*)p = z;
+  *(bf16x8*)(p + 8) = z;
+}
+
+// Length of batch row `b`, clamped into [0, S] so that no entry can
+// index outside the sequence.
+__device__ __forceinline__ int clamped_len(const int* seqlens, int b,
+                                           int S) {
+  return min(max(seqlens[b], 0), S);
+}
+
 // ------------------------------------------------ pre-transpose pass
 // T[bh][d][s] = X(bh, s, d) where X rows are `rs` elements apart.
 // One workgroup per (bh, 64-row s-block); LDS 64x64 transpose with
@@ -148,11 +187,13 @@ __global__ __launch_bounds__(ATHREADS) void attn_pretranspose_k(
 
 // ------------------------------------------------------------- fwd
 
+template <bool VARLEN>
 __global__ __launch_bounds__(ATHREADS) void attn_fwd_k(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ VT, short* __restrict__ O,
     float* __restrict__ LSE, const long long* __restrict__ seed_p,
-    int S, int H, int rs, int ors, unsigned p24, float inv1mp) {
+    int S, int H, int rs, int ors, unsigned p24, float inv1mp,
+    const int* __restrict__ seqlens) {
   __shared__ short lK[2][TILE_ELEMS];   // [key][d], double-buffered
   __shared__ short lVt[2][TILE_ELEMS];  // [d][key]
   __shared__ short lP[TILE_ELEMS];
@@ -164,6 +205,16 @@ __global__ __launch_bounds__(ATHREADS) void attn_fwd_k(
   const long long obase =
       ((long long)(bh / H) * S) * ors + (long long)(bh % H) * 64;
   const short* vtb = VT + (long long)bh * 64 * S;
+  int len = S;
+  if constexpr (VARLEN) {
+    len = clamped_len(seqlens, bh / H, S);
+    if (qt * BQ >= len) {  // block-uniform: the whole Q tile is padding
+      zero_tile(O + obase + (long long)qt * BQ * ors, ors, threadIdx.x);
+      if (LSE && threadIdx.x < BQ)
+        LSE[(long long)bh * S + qt * BQ + threadIdx.x] = 0.f;
+      return;
+    }
+  }
   const unsigned seed = seed_p ? (unsigned)(*seed_p) : 0u;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -198,7 +249,8 @@ __global__ __launch_bounds__(ATHREADS) void attn_fwd_k(
 #pragma unroll
   for (int df = 0; df < 4; ++df) o_acc[df] = {0.f, 0.f, 0.f, 0.f};
 
-  const int ntiles = S / BKV;
+  // VARLEN: only the tiles that hold a valid key (each holds >= 1)
+  const int ntiles = VARLEN ? (len + BKV - 1) / BKV : S / BKV;
   stage_tile(lK[0], K + base, rs, tid);
   stage_tile(lVt[0], vtb, S, tid);
   __builtin_amdgcn_s_waitcnt(0);
@@ -225,6 +277,17 @@ __global__ __launch_bounds__(ATHREADS) void attn_fwd_k(
       }
     }
 
+    // VARLEN: keys of this tile at or beyond kvalid are padding (only
+    // in the tail tile); they leave the running max and get p = 0
+    const int kvalid = VARLEN ? len - t * BKV : BKV;
+    if constexpr (VARLEN) {
+#pragma unroll
+      for (int kf = 0; kf < 4; ++kf)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (kf * 16 + c_col >= kvalid) s_acc[kf][r] = -1e30f;
+    }
+
     float pmax[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -244,7 +307,8 @@ __global__ __launch_bounds__(ATHREADS) void attn_fwd_k(
       float rowsum = 0.f;
 #pragma unroll
       for (int kf = 0; kf < 4; ++kf) {
-        const float p = __expf(s_acc[kf][r] - m_new);
+        float p = __expf(s_acc[kf][r] - m_new);
+        if constexpr (VARLEN) p = kf * 16 + c_col < kvalid ? p : 0.f;
         rowsum += p;  // l accumulates the UNdropped probabilities
         const float keep = drop_keep(seed, bh, qrow,
                                      t * BKV + kf * 16 + c_col, S, p24,
@@ -290,19 +354,29 @@ __global__ __launch_bounds__(ATHREADS) void attn_fwd_k(
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int qrow = qrow0 + c_sub_row + r;
-      O[obase + (long long)qrow * ors + df * 16 + c_col] =
-          f2bf(o_acc[df][r] / l_run[r]);
+      if constexpr (VARLEN)  // tail Q tile: padded rows store zero
+        O[obase + (long long)qrow * ors + df * 16 + c_col] =
+            qrow < len ? f2bf(o_acc[df][r] / l_run[r]) : (short)0;
+      else
+        O[obase + (long long)qrow * ors + df * 16 + c_col] =
+            f2bf(o_acc[df][r] / l_run[r]);
     }
   if (LSE && c_col == 0) {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      LSE[(long long)bh * S + qrow0 + c_sub_row + r] =
-          m_run[r] + __logf(l_run[r]);
+      if constexpr (VARLEN)
+        LSE[(long long)bh * S + qrow0 + c_sub_row + r] =
+            qrow0 + c_sub_row + r < len ? m_run[r] + __logf(l_run[r])
+                                        : 0.f;
+      else
+        LSE[(long long)bh * S + qrow0 + c_sub_row + r] =
+            m_run[r] + __logf(l_run[r]);
   }
 }
 
 // --------------------------------------------------------- bwd dK/dV
 
+template <bool VARLEN>
 __global__ __launch_bounds__(ATHREADS) void attn_bwd_dkdv_k(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, const short* __restrict__ dO,
@@ -310,7 +384,8 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dkdv_k(
     const float* __restrict__ LSE, const float* __restrict__ Drow,
     short* __restrict__ dK, short* __restrict__ dV,
     const long long* __restrict__ seed_p, int S, int H, int rs, int ors,
-    int grs, unsigned p24, float inv1mp) {
+    int grs, unsigned p24, float inv1mp,
+    const int* __restrict__ seqlens) {
   __shared__ short lQ[2][TILE_ELEMS];    // [q][d]
   __shared__ short lQt[2][TILE_ELEMS];   // [d][q]
   __shared__ short ldO[2][TILE_ELEMS];   // [q][d]
@@ -327,6 +402,15 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dkdv_k(
       ((long long)(bh / H) * S) * grs + (long long)(bh % H) * 64;
   const short* qtb = QT + (long long)bh * 64 * S;
   const short* dtb = DOT + (long long)bh * 64 * S;
+  int len = S;
+  if constexpr (VARLEN) {
+    len = clamped_len(seqlens, bh / H, S);
+    if (kt * BKV >= len) {  // block-uniform: the whole key tile is padding
+      zero_tile(dK + gbase + (long long)kt * BKV * grs, grs, threadIdx.x);
+      zero_tile(dV + gbase + (long long)kt * BKV * grs, grs, threadIdx.x);
+      return;
+    }
+  }
   const unsigned seed = seed_p ? (unsigned)(*seed_p) : 0u;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -365,7 +449,8 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dkdv_k(
     stage_tile(ldOt[buf], dtb + it * BQ, S, tid);
   };
 
-  const int ntiles = S / BQ;
+  // VARLEN: Q tiles beyond the length contribute nothing
+  const int ntiles = VARLEN ? (len + BQ - 1) / BQ : S / BQ;
   stage_q(0, 0);
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
@@ -402,9 +487,17 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dkdv_k(
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = kt * BKV + wave * 16 + c_sub_row + r;
-        const float p = __expf(st[qf][r] * qscale - lse);
+        float p = __expf(st[qf][r] * qscale - lse);
         const float keep = drop_keep(seed, bh, q, key, S, p24, inv1mp);
-        dpt[qf][r] = p * (dpt[qf][r] * keep - di) * qscale;  // dS^T*sc
+        float dst = p * (dpt[qf][r] * keep - di) * qscale;  // dS^T*sc
+        if constexpr (VARLEN) {
+          // padded query or key: lse/di may hold anything, so select
+          // zeros instead of multiplying by one
+          const bool valid = q < len && key < len;
+          p = valid ? p : 0.f;
+          dst = valid ? dst : 0.f;
+        }
+        dpt[qf][r] = dst;
         lds_st16(lT,
                  (wave * 16 + c_sub_row + r) * BQ + qf * 16 + c_col,
                  f2bf(p * keep));
@@ -458,20 +551,28 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dkdv_k(
     for (int r = 0; r < 4; ++r) {
       const long long off = gbase +
           (long long)(krow0 + c_sub_row + r) * grs + df * 16 + c_col;
-      dK[off] = f2bf(dk[df][r]);
-      dV[off] = f2bf(dv[df][r]);
+      if constexpr (VARLEN) {  // tail key tile: padded rows store zero
+        const bool valid = krow0 + c_sub_row + r < len;
+        dK[off] = valid ? f2bf(dk[df][r]) : (short)0;
+        dV[off] = valid ? f2bf(dv[df][r]) : (short)0;
+      } else {
+        dK[off] = f2bf(dk[df][r]);
+        dV[off] = f2bf(dv[df][r]);
+      }
     }
 }
 
 // ----------------------------------------------------------- bwd dQ
 
+template <bool VARLEN>
 __global__ __launch_bounds__(ATHREADS) void attn_bwd_dq_k(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, const short* __restrict__ dO,
     const short* __restrict__ KT, const float* __restrict__ LSE,
     const float* __restrict__ Drow, short* __restrict__ dQ,
     const long long* __restrict__ seed_p, int S, int H, int rs, int ors,
-    int grs, unsigned p24, float inv1mp) {
+    int grs, unsigned p24, float inv1mp,
+    const int* __restrict__ seqlens) {
   __shared__ short lK[2][TILE_ELEMS];   // [key][d]
   __shared__ short lKt[2][TILE_ELEMS];  // [d][key]
   __shared__ short lV[2][TILE_ELEMS];   // [key][d]
@@ -486,6 +587,14 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dq_k(
   const long long gbase =
       ((long long)(bh / H) * S) * grs + (long long)(bh % H) * 64;
   const short* ktb = KT + (long long)bh * 64 * S;
+  int len = S;
+  if constexpr (VARLEN) {
+    len = clamped_len(seqlens, bh / H, S);
+    if (qt * BQ >= len) {  // block-uniform: the whole Q tile is padding
+      zero_tile(dQ + gbase + (long long)qt * BQ * grs, grs, threadIdx.x);
+      return;
+    }
+  }
   const unsigned seed = seed_p ? (unsigned)(*seed_p) : 0u;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -529,7 +638,7 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dq_k(
     stage_tile(lV[buf], V + base + (long long)t * BKV * rs, rs, tid);
   };
 
-  const int ntiles = S / BKV;
+  const int ntiles = VARLEN ? (len + BKV - 1) / BKV : S / BKV;
   stage_kv(0, 0);
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
@@ -564,7 +673,9 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dq_k(
         const int key = t * BKV + kf * 16 + c_col;
         const float p = __expf(s_acc[kf][r] - lse[r]);
         const float keep = drop_keep(seed, bh, q, key, S, p24, inv1mp);
-        const float ds = p * (dp[kf][r] * keep - di[r]) * qscale;
+        float ds = p * (dp[kf][r] * keep - di[r]) * qscale;
+        // padded query or key: select zero (lse/di may hold anything)
+        if constexpr (VARLEN) ds = q < len && key < len ? ds : 0.f;
         lds_st16(lDS,
                  (wave * 16 + c_sub_row + r) * BKV + kf * 16 + c_col,
                  f2bf(ds));
@@ -591,9 +702,12 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dq_k(
 #pragma unroll
   for (int df = 0; df < 4; ++df)
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-      dQ[gbase + (long long)(qrow0 + c_sub_row + r) * grs + df * 16 +
-         c_col] = f2bf(dq[df][r]);
+    for (int r = 0; r < 4; ++r) {
+      const int qrow = qrow0 + c_sub_row + r;
+      short g = f2bf(dq[df][r]);
+      if constexpr (VARLEN) g = qrow < len ? g : (short)0;
+      dQ[gbase + (long long)qrow * grs + df * 16 + c_col] = g;
+    }
 }
 
 }  // namespace
@@ -607,12 +721,14 @@ void launch_attn_pretranspose(const short* X, short* T, int BH, int S,
 void launch_attn_fwd(const short* Q, const short* K, const short* VT,
                      short* O, float* LSE, const long long* seed, int BH,
                      int S, int H, int rs, int ors, float dropout_p,
-                     hipStream_t stream) {
+                     const int* seqlens, hipStream_t stream) {
   const unsigned p24 = (unsigned)(dropout_p * 16777216.0f);
   const float inv1mp = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
-  hipLaunchKernelGGL(attn_fwd_k, dim3(BH, S / BQ), dim3(ATHREADS), 0,
-                     stream, Q, K, VT, O, LSE, seed, S, H, rs, ors, p24,
-                     inv1mp);
+  // no lengths: the fixed-length instantiation, untouched by VARLEN
+  auto* fwd = seqlens ? attn_fwd_k<true> : attn_fwd_k<false>;
+  hipLaunchKernelGGL(fwd, dim3(BH, S / BQ), dim3(ATHREADS), 0, stream, Q,
+                     K, VT, O, LSE, seed, S, H, rs, ors, p24, inv1mp,
+                     seqlens);
 }
 
 void launch_attn_bwd(const short* Q, const short* K, const short* V,
@@ -621,13 +737,15 @@ void launch_attn_bwd(const short* Q, const short* K, const short* V,
                      short* dQ, short* dK, short* dV,
                      const long long* seed, int BH, int S, int H, int rs,
                      int ors, int grs, float dropout_p,
-                     hipStream_t stream) {
+                     const int* seqlens, hipStream_t stream) {
   const unsigned p24 = (unsigned)(dropout_p * 16777216.0f);
   const float inv1mp = dropout_p > 0.f ? 1.f / (1.f - dropout_p) : 1.f;
-  hipLaunchKernelGGL(attn_bwd_dkdv_k, dim3(BH, S / BKV), dim3(ATHREADS),
-                     0, stream, Q, K, V, dO, QT, DOT, LSE, Drow, dK, dV,
-                     seed, S, H, rs, ors, grs, p24, inv1mp);
-  hipLaunchKernelGGL(attn_bwd_dq_k, dim3(BH, S / BQ), dim3(ATHREADS), 0,
-                     stream, Q, K, V, dO, KT, LSE, Drow, dQ, seed, S, H,
-                     rs, ors, grs, p24, inv1mp);
+  auto* dkdv = seqlens ? attn_bwd_dkdv_k<true> : attn_bwd_dkdv_k<false>;
+  auto* dq = seqlens ? attn_bwd_dq_k<true> : attn_bwd_dq_k<false>;
+  hipLaunchKernelGGL(dkdv, dim3(BH, S / BKV), dim3(ATHREADS), 0, stream,
+                     Q, K, V, dO, QT, DOT, LSE, Drow, dK, dV, seed, S, H,
+                     rs, ors, grs, p24, inv1mp, seqlens);
+  hipLaunchKernelGGL(dq, dim3(BH, S / BQ), dim3(ATHREADS), 0, stream, Q,
+                     K, V, dO, KT, LSE, Drow, dQ, seed, S, H, rs, ors,
+                     grs, p24, inv1mp, seqlens);
 }

@@ -327,9 +327,28 @@ static const long long* seed_ptr(const c10::optional<at::Tensor>& seed) {
   return reinterpret_cast<const long long*>(seed->data_ptr<int64_t>());
 }
 
+// Per-sequence lengths of a right-padded batch: int32 on the data's
+// device, one entry per batch row (`rows` = B for the packed layout, BH
+// for plain [BH,S,64]). The VALUES stay on the device (the kernels
+// clamp them into [0,S]); only the metadata is validated here.
+static const int* seqlens_ptr(const c10::optional<at::Tensor>& seqlens,
+                              const at::Tensor& like, int64_t rows) {
+  if (!seqlens.has_value()) return nullptr;
+  TORCH_CHECK(seqlens->is_cuda(), "seqlens must be on GPU");
+  TORCH_CHECK(seqlens->device() == like.device(),
+              "seqlens must be on the same device as the data");
+  TORCH_CHECK(seqlens->scalar_type() == at::kInt,
+              "seqlens must be int32");
+  TORCH_CHECK(seqlens->is_contiguous(), "seqlens must be contiguous");
+  TORCH_CHECK(seqlens->numel() == rows, "seqlens must hold ", rows,
+              " entries, got ", seqlens->numel());
+  return seqlens->data_ptr<int>();
+}
+
 std::vector<at::Tensor> attn_fwd(const at::Tensor& Q, const at::Tensor& K,
                                  const at::Tensor& V, double dropout_p,
-                                 const c10::optional<at::Tensor>& seed) {
+                                 const c10::optional<at::Tensor>& seed,
+                                 const c10::optional<at::Tensor>& seqlens) {
   CHECK_BF16_CUDA(Q);
   CHECK_BF16_CUDA(K);
   CHECK_BF16_CUDA(V);
@@ -340,6 +359,7 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& Q, const at::Tensor& K,
   TORCH_CHECK(S % 64 == 0, "attn_fwd requires S % 64 == 0");
   TORCH_CHECK(dropout_p == 0.0 || seed.has_value(),
               "dropout needs a seed tensor");
+  const int* lens = seqlens_ptr(seqlens, Q, BH);
   DeviceGuard guard(Q.device());
   auto O = at::empty_like(Q);
   auto LSE = at::empty({BH, S}, Q.options().dtype(at::kFloat));
@@ -348,13 +368,14 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& Q, const at::Tensor& K,
                            cur_stream());
   launch_attn_fwd(bf_ptr(Q), bf_ptr(K), bf_ptr(VT), bf_ptr_mut(O),
                   LSE.data_ptr<float>(), seed_ptr(seed), BH, S, 1, 64,
-                  64, (float)dropout_p, cur_stream());
+                  64, (float)dropout_p, lens, cur_stream());
   return {O, LSE};
 }
 
 std::vector<at::Tensor> attn_fwd_packed(
     const at::Tensor& qkv, double dropout_p,
-    const c10::optional<at::Tensor>& seed) {
+    const c10::optional<at::Tensor>& seed,
+    const c10::optional<at::Tensor>& seqlens) {
   CHECK_BF16_CUDA(qkv);
   TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3 && qkv.size(4) == 64 &&
                   qkv.is_contiguous(),
@@ -363,6 +384,7 @@ std::vector<at::Tensor> attn_fwd_packed(
             H = (int)qkv.size(3);
   TORCH_CHECK(S % 64 == 0, "attn requires S % 64 == 0");
   TORCH_CHECK(dropout_p == 0.0 || seed.has_value());
+  const int* lens = seqlens_ptr(seqlens, qkv, B);
   DeviceGuard guard(qkv.device());
   auto O = at::empty({B, S, H * 64}, qkv.options());
   auto LSE = at::empty({B * H, S}, qkv.options().dtype(at::kFloat));
@@ -372,7 +394,7 @@ std::vector<at::Tensor> attn_fwd_packed(
                            B * H, S, H, 3 * H * 64, cur_stream());
   launch_attn_fwd(base, base + (long long)H * 64, bf_ptr(VT),
                   bf_ptr_mut(O), LSE.data_ptr<float>(), seed_ptr(seed),
-                  B * H, S, H, 3 * H * 64, H * 64, (float)dropout_p,
+                  B * H, S, H, 3 * H * 64, H * 64, (float)dropout_p, lens,
                   cur_stream());
   return {O, LSE};
 }
@@ -381,12 +403,27 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& Q, const at::Tensor& K,
                                  const at::Tensor& V, const at::Tensor& dO,
                                  const at::Tensor& LSE,
                                  const at::Tensor& Drow, double dropout_p,
-                                 const c10::optional<at::Tensor>& seed) {
+                                 const c10::optional<at::Tensor>& seed,
+                                 const c10::optional<at::Tensor>& seqlens) {
   CHECK_BF16_CUDA(Q);
+  CHECK_BF16_CUDA(K);
+  CHECK_BF16_CUDA(V);
   CHECK_BF16_CUDA(dO);
   CHECK_F32_CUDA(LSE);
   CHECK_F32_CUDA(Drow);
+  // same shape contract as attn_fwd: the kernels index every operand
+  // with Q's [BH, S, 64] extents
+  TORCH_CHECK(Q.dim() == 3 && Q.size(2) == 64 && Q.sizes() == K.sizes() &&
+                  Q.sizes() == V.sizes() && Q.sizes() == dO.sizes(),
+              "attn_bwd expects [BH, S, 64] bf16 q/k/v/dO of equal sizes");
   const int BH = (int)Q.size(0), S = (int)Q.size(1);
+  TORCH_CHECK(S % 64 == 0, "attn_bwd requires S % 64 == 0");
+  TORCH_CHECK(LSE.dim() == 2 && LSE.size(0) == BH && LSE.size(1) == S &&
+                  LSE.sizes() == Drow.sizes(),
+              "attn_bwd expects [BH, S] fp32 LSE and Drow");
+  TORCH_CHECK(dropout_p == 0.0 || seed.has_value(),
+              "dropout needs a seed tensor");
+  const int* lens = seqlens_ptr(seqlens, Q, BH);
   DeviceGuard guard(Q.device());
   auto dQ = at::empty_like(Q);
   auto dK = at::empty_like(K);
@@ -402,22 +439,33 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& Q, const at::Tensor& K,
                   ktt, LSE.data_ptr<float>(), Drow.data_ptr<float>(),
                   bf_ptr_mut(dQ), bf_ptr_mut(dK), bf_ptr_mut(dV),
                   seed_ptr(seed), BH, S, 1, 64, 64, 64, (float)dropout_p,
-                  cur_stream());
+                  lens, cur_stream());
   return {dQ, dK, dV};
 }
 
 at::Tensor attn_bwd_packed(const at::Tensor& qkv, const at::Tensor& dO,
                            const at::Tensor& LSE, const at::Tensor& Drow,
                            double dropout_p,
-                           const c10::optional<at::Tensor>& seed) {
+                           const c10::optional<at::Tensor>& seed,
+                           const c10::optional<at::Tensor>& seqlens) {
   CHECK_BF16_CUDA(qkv);
   CHECK_BF16_CUDA(dO);
   CHECK_F32_CUDA(LSE);
   CHECK_F32_CUDA(Drow);
-  TORCH_CHECK(qkv.dim() == 5 && qkv.is_contiguous() &&
-              dO.is_contiguous());
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3 && qkv.size(4) == 64,
+              "attn_bwd_packed expects contiguous [B,S,3,H,64] bf16");
   const int B = (int)qkv.size(0), S = (int)qkv.size(1),
             H = (int)qkv.size(3);
+  TORCH_CHECK(S % 64 == 0, "attn requires S % 64 == 0");
+  TORCH_CHECK(dO.dim() == 3 && dO.size(0) == B && dO.size(1) == S &&
+                  dO.size(2) == (int64_t)H * 64,
+              "attn_bwd_packed expects dO [B, S, H*64]");
+  TORCH_CHECK(LSE.dim() == 2 && LSE.size(0) == (int64_t)B * H &&
+                  LSE.size(1) == S && LSE.sizes() == Drow.sizes(),
+              "attn_bwd_packed expects [B*H, S] fp32 LSE and Drow");
+  TORCH_CHECK(dropout_p == 0.0 || seed.has_value(),
+              "dropout needs a seed tensor");
+  const int* lens = seqlens_ptr(seqlens, qkv, B);
   DeviceGuard guard(qkv.device());
   auto dqkv = at::empty_like(qkv);
   const short* base = bf_ptr(qkv);
@@ -438,7 +486,7 @@ at::Tensor attn_bwd_packed(const at::Tensor& qkv, const at::Tensor& dO,
                   gbase + (long long)H * 64,
                   gbase + (long long)2 * H * 64, seed_ptr(seed), BH, S,
                   H, 3 * H * 64, H * 64, 3 * H * 64, (float)dropout_p,
-                  cur_stream());
+                  lens, cur_stream());
   return dqkv;
 }
 
@@ -507,12 +555,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Streaming tall-skinny GEMM (1x1 convs)");
   m.def("wgrad_splitk", &wgrad_splitk,
         "Split-M wgrad GEMM (tr_b16 fragment path)");
-  m.def("attn_fwd", &attn_fwd, "Flash attention fwd (D=64, bf16)");
-  m.def("attn_bwd", &attn_bwd, "Flash attention bwd (dQ/dK/dV)");
+  // trailing seqlens defaults to None, so the five-/six-/eight-argument
+  // positional calls from before variable-length support keep working
+  m.def("attn_fwd", &attn_fwd, "Flash attention fwd (D=64, bf16)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dropout_p"),
+        py::arg("seed"), py::arg("seqlens") = py::none());
+  m.def("attn_bwd", &attn_bwd, "Flash attention bwd (dQ/dK/dV)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dO"),
+        py::arg("lse"), py::arg("drow"), py::arg("dropout_p"),
+        py::arg("seed"), py::arg("seqlens") = py::none());
   m.def("attn_fwd_packed", &attn_fwd_packed,
-        "Flash attention fwd over the packed qkv buffer");
+        "Flash attention fwd over the packed qkv buffer", py::arg("qkv"),
+        py::arg("dropout_p"), py::arg("seed"),
+        py::arg("seqlens") = py::none());
   m.def("attn_bwd_packed", &attn_bwd_packed,
-        "Flash attention bwd -> packed dqkv");
+        "Flash attention bwd -> packed dqkv", py::arg("qkv"),
+        py::arg("dO"), py::arg("lse"), py::arg("drow"),
+        py::arg("dropout_p"), py::arg("seed"),
+        py::arg("seqlens") = py::none());
   m.def("gbt_histogram", &gbt_histogram, "GBT g/h histogram (N7)");
   m.def("bn_fwd", &bn_fwd, "Fused BatchNorm(+add)(+ReLU) fwd (bf16 NHWC)");
   m.def("bn_bwd", &bn_bwd, "Fused BatchNorm(+add)(+ReLU) bwd (bf16 NHWC)");

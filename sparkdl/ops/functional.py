@@ -27,6 +27,72 @@ def bias_gelu_ref(x, bias):
         x.float() + bias.float(), approximate="none").to(x.dtype)
 
 
+def masked_attention_ref(q, k, v, seq_lens, dropout_p=0.0):
+    """Attention over a right-padded batch: row ``n`` of the leading
+    dim holds ``seq_lens[n]`` valid tokens at positions ``[0, len)``.
+
+    q/k/v: ``[N, ..., S, d]`` (``[BH,S,d]`` or ``[B,h,S,d]``); seq_lens:
+    integer ``[N]`` (clamped into ``[0, S]``). For ``q < len``:
+    ``O[q] = softmax_{k < len}(q.k / sqrt(d)) @ V[:len]``. Query rows
+    ``>= len`` give exactly zero and act as constants for autograd: no
+    dQ, no contribution to dK/dV, and dK/dV rows ``>= len`` are zero.
+    ``len == 0`` gives all-zero output and gradients without NaN.
+
+    Scores are masked with the finite fp32 minimum, not ``-inf``: an
+    all-``-inf`` row (length 0) would make the softmax NaN, and that
+    NaN survives into the backward even when the forward is zeroed. P
+    is then zeroed by selection wherever the key or the query is
+    padding."""
+    S, d = q.shape[-2], q.shape[-1]
+    qf, kf, vf = q.float(), k.float(), v.float()
+    lens = torch.as_tensor(seq_lens, device=q.device).clamp(0, S)
+    lens = lens.reshape((-1,) + (1,) * (q.dim() - 2))
+    valid = torch.arange(S, device=q.device) < lens    # [N, ..., S]
+    kmask = valid.unsqueeze(-2)
+    qmask = valid.unsqueeze(-1)
+    # fp32 throughout, also when called under autocast (the fill value
+    # does not fit a 16-bit score matrix)
+    with torch.autocast(q.device.type, enabled=False):
+        s = qf @ kf.transpose(-1, -2) / d ** 0.5
+        s = s.masked_fill(~kmask, torch.finfo(torch.float32).min)
+        p = torch.softmax(s, dim=-1)
+        p = torch.where(kmask & qmask, p, p.new_zeros(()))
+        if dropout_p > 0:
+            p = torch.nn.functional.dropout(p, dropout_p)
+        o = p @ vf
+    return o.to(q.dtype)
+
+
+def seqlens_from_mask(attention_mask, validate=None):
+    """``[B, S]`` bool/integer key-padding mask (nonzero = token) ->
+    int32 ``[B]`` lengths on the mask's device, by a device-side sum.
+
+    The attention kernels take right-padded batches only, so with
+    ``validate=True`` every row must be a prefix of ones (no holes, no
+    left padding), else ``ValueError``. That check reads one flag back
+    to the host. The default validates except while the current stream
+    is being captured into a graph, where a host sync is illegal.
+    Passing ``seq_lens`` directly to the attention / model entry points
+    is the path with no sync at all."""
+    m = attention_mask
+    if m.dim() != 2:
+        raise ValueError("attention_mask must be [B, S], got %s"
+                         % (tuple(m.shape),))
+    mb = m != 0
+    lens = mb.sum(-1, dtype=torch.int32)
+    if validate is None:
+        validate = not (m.is_cuda
+                        and torch.cuda.is_current_stream_capturing())
+    if validate:
+        prefix = torch.arange(m.shape[1], device=m.device) \
+            < lens.unsqueeze(-1)
+        if not bool((mb == prefix).all()):
+            raise ValueError(
+                "attention_mask must be right-padded: every row a run "
+                "of ones followed by zeros (no holes, no left padding)")
+    return lens
+
+
 # ---------------------------------------------------------------------------
 # Autograd bindings
 # ---------------------------------------------------------------------------
@@ -237,10 +303,12 @@ def _attn_seed_tensor(device):
 
 class _FlashAttnFn(torch.autograd.Function):
     """O = softmax(Q K^T / sqrt(64)) V with optional attention-prob
-    dropout. q/k/v: [BH, S, 64] bf16 contiguous, S % 64 == 0."""
+    dropout. q/k/v: [BH, S, 64] bf16 contiguous, S % 64 == 0.
+    seq_lens (optional): int32 [BH] on the same device — right-padded
+    rows, masked_attention_ref semantics; it gets no gradient."""
 
     @staticmethod
-    def forward(ctx, q, k, v, dropout_p):
+    def forward(ctx, q, k, v, dropout_p, seq_lens=None):
         C = _ops.ext()
         seed = None
         if dropout_p > 0:
@@ -249,35 +317,43 @@ class _FlashAttnFn(torch.autograd.Function):
             # the backward must replay this step's seed even if later
             # steps advanced the counter
             seed = seed.clone()
-        o, lse = C.attn_fwd(q, k, v, float(dropout_p), seed)
+        o, lse = C.attn_fwd(q, k, v, float(dropout_p), seed, seq_lens)
         ctx.save_for_backward(q, k, v, o, lse,
                               seed if seed is not None else
-                              torch.empty(0))
+                              torch.empty(0), seq_lens)
         ctx.dropout_p = float(dropout_p)
         return o
 
     @staticmethod
     def backward(ctx, do):
         C = _ops.ext()
-        q, k, v, o, lse, seed = ctx.saved_tensors
+        q, k, v, o, lse, seed, seq_lens = ctx.saved_tensors
         if seed.numel() == 0:
             seed = None
         do = do.contiguous()
         # D_i = rowsum(dO o O), fp32 (flash backward precompute)
         drow = (do.float() * o.float()).sum(-1)
         dq, dk, dv = C.attn_bwd(q, k, v, do, lse, drow, ctx.dropout_p,
-                                seed)
-        return dq, dk, dv, None
+                                seed, seq_lens)
+        return dq, dk, dv, None, None
 
 
-def flash_attention(q, k, v, dropout_p=0.0):
+def flash_attention(q, k, v, dropout_p=0.0, seq_lens=None):
     """[B, h, S, d] attention through the hand-written kernels; the
-    caller checks flash_attention_ok first."""
+    caller checks flash_attention_ok first.
+
+    seq_lens (optional): int32 [B] on q's device, the valid length of
+    each right-padded batch row (masked_attention_ref semantics: padded
+    query rows come back exactly zero). The lengths are only ever read
+    on the device, so the call stays sync-free and graph-capturable."""
     B, h, S, d = q.shape
     q3 = q.reshape(B * h, S, d).contiguous()
     k3 = k.reshape(B * h, S, d).contiguous()
     v3 = v.reshape(B * h, S, d).contiguous()
-    o = _FlashAttnFn.apply(q3, k3, v3, dropout_p)
+    if seq_lens is not None:
+        # the [BH,S,64] kernels index lengths per bh
+        seq_lens = seq_lens.view(B, 1).expand(B, h).reshape(B * h)
+    o = _FlashAttnFn.apply(q3, k3, v3, dropout_p, seq_lens)
     return o.view(B, h, S, d)
 
 
@@ -294,24 +370,24 @@ class _FlashAttnPackedFn(torch.autograd.Function):
     contiguous copies anywhere around the attention."""
 
     @staticmethod
-    def forward(ctx, qkv, dropout_p):
+    def forward(ctx, qkv, dropout_p, seq_lens=None):
         C = _ops.ext()
         seed = None
         if dropout_p > 0:
             seed = _attn_seed_tensor(qkv.device)
             seed.add_(1)
             seed = seed.clone()
-        o, lse = C.attn_fwd_packed(qkv, float(dropout_p), seed)
+        o, lse = C.attn_fwd_packed(qkv, float(dropout_p), seed, seq_lens)
         ctx.save_for_backward(qkv, o, lse,
                               seed if seed is not None else
-                              torch.empty(0))
+                              torch.empty(0), seq_lens)
         ctx.dropout_p = float(dropout_p)
         return o
 
     @staticmethod
     def backward(ctx, do):
         C = _ops.ext()
-        qkv, o, lse, seed = ctx.saved_tensors
+        qkv, o, lse, seed, seq_lens = ctx.saved_tensors
         if seed.numel() == 0:
             seed = None
         do = do.contiguous()
@@ -320,13 +396,24 @@ class _FlashAttnPackedFn(torch.autograd.Function):
         # D_i = rowsum(dO o O) per (b,h,s): [B,S,H] -> [B*H, S]
         drow = (do.float() * o.float()).view(B, S, H, 64).sum(-1) \
             .transpose(1, 2).reshape(B * H, S).contiguous()
-        dqkv = C.attn_bwd_packed(qkv, do, lse, drow, ctx.dropout_p, seed)
-        return dqkv, None
+        dqkv = C.attn_bwd_packed(qkv, do, lse, drow, ctx.dropout_p, seed,
+                                 seq_lens)
+        return dqkv, None, None
 
 
-def flash_attention_packed(qkv, dropout_p=0.0):
-    """qkv: [B, S, 3, H, 64] bf16 contiguous -> O [B, S, H*64]."""
-    return _FlashAttnPackedFn.apply(qkv.contiguous(), dropout_p)
+def flash_attention_packed(qkv, dropout_p=0.0, seq_lens=None):
+    """qkv: [B, S, 3, H, 64] bf16 contiguous -> O [B, S, H*64].
+
+    seq_lens (optional): int32 [B] on qkv's device, the valid length of
+    each right-padded batch row. Row b attends over keys [0, len_b);
+    O rows >= len_b and the matching dqkv rows are exactly zero, and
+    the kernels skip whole 64-wide tiles beyond len_b, so a padded
+    batch costs about len^2, not S^2. Lengths are read on the device
+    only: no host sync, graph-capturable, and the tensor may be
+    refilled in place between graph replays. seqlens_from_mask turns an
+    attention_mask into lengths (its validation syncs; passing seq_lens
+    is the sync-free path)."""
+    return _FlashAttnPackedFn.apply(qkv.contiguous(), dropout_p, seq_lens)
 
 
 def _conv_gemm(a2d, w):
