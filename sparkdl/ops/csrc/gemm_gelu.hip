@@ -27,7 +27,8 @@
 //     optional pre-activation Z for the backward pass
 //   - edges: A/B row indices clamp to the last valid row (out-of-range
 //     rows compute garbage in out-of-range outputs only), C/Z stores
-//     are predicated; host requires only K % 64 == 0.
+//     are predicated (N % 8 != 0 stores element-wise: its rows are not
+//     16-byte aligned); host requires only K % 64 == 0.
 //
 // MFMA fragment layout for mfma_f32_16x16x32_bf16 (HW-verified):
 // A-operand lane l holds A[row=l%16][k=8*(l/16)..+8]; B-operand lane l
@@ -190,7 +191,12 @@ __global__ __launch_bounds__(kThreads) void gemm_bias_act_k(
     __builtin_amdgcn_s_barrier();
   };
   auto store_out = [&](short* __restrict__ dst) {
-    // 1024 threads x 16 B = 32 rows per sweep; 8 sweeps for 256 rows
+    // 1024 threads x 16 B = 32 rows per sweep; 8 sweeps for 256 rows.
+    // The bf16x8 store needs a 16-byte aligned address: the base is an
+    // allocation start and gcol a multiple of 8, so row offsets grow*N
+    // are aligned for every row only when N % 8 == 0. Other N take the
+    // element-wise path for the whole tile.
+    const bool vec_rows = (N & 7) == 0;
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const int row = s * 32 + tid / 32;
@@ -199,7 +205,7 @@ __global__ __launch_bounds__(kThreads) void gemm_bias_act_k(
       const int col = (tid % 32) * 8;
       const long long gcol = b_row0 + col;
       const bf16x8 v = *(const bf16x8*)&lds[row * kBN + col];
-      if (gcol + 8 <= N) {
+      if (vec_rows && gcol + 8 <= N) {
         *(bf16x8*)&dst[grow * N + gcol] = v;
       } else {
         for (int u = 0; u < 8 && gcol + u < N; ++u)
