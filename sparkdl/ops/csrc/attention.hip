@@ -20,9 +20,8 @@
 // compute(t), one vmcnt(0)+barrier per tile (the guide's minimum
 // 2-phase pattern).
 //
-// All matrix products use the one HW-verified mfma_f32_16x16x32_bf16
-// fragment path (operands K-major; C/D lane l reg r =
-// C[(l/16)*4+r][l%16]):
+// All matrix products use the one mfma_f32_16x16x32_bf16 fragment path
+// of mfma_tile.hip.h (operands K-major):
 //   fwd:   S   = mfma(Q, K)        P->LDS   O  = mfma(P_lds, Vt)
 //   dK/dV: S^T = mfma(K, Q)        dP^T = mfma(V, dO)
 //          dV  = mfma(PmT_lds, dOt)  dK = mfma(dST_lds, Qt)
@@ -65,7 +64,7 @@
 // wave's rows, so they need no barriers (same-wave LDS ops complete in
 // order).
 
-#include "common.hip.h"
+#include "mfma_tile.hip.h"
 #include "kernels.h"
 
 namespace {
@@ -75,15 +74,6 @@ constexpr int BQ = 64;
 constexpr int BKV = 64;
 constexpr int ATHREADS = 256;
 constexpr int TILE_ELEMS = 64 * 64;
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float bf2f(short s) {
-  union { float f; unsigned u; } c;
-  c.u = ((unsigned)(unsigned short)s) << 16;
-  return c.f;
-}
 
 __device__ __forceinline__ unsigned drop_hash(unsigned seed,
                                               unsigned idx) {
@@ -105,31 +95,27 @@ __device__ __forceinline__ float drop_keep(unsigned seed,
   return (drop_hash(seed, idx) & 0xffffffu) >= p24 ? inv1mp : 0.f;
 }
 
-__device__ __forceinline__ int aswz(int byte_off) {
-  return byte_off ^ (((byte_off >> 7) & 7) << 4);
-}
-__device__ __forceinline__ void lds_st16(short* base, int elem,
-                                         short v) {
-  *(short*)((char*)base + aswz(elem * 2)) = v;
-}
-__device__ __forceinline__ bf16x8 lds_ld128(const short* base, int row,
-                                            int kk) {
-  return *(const bf16x8*)((const char*)base + aswz((row * 64 + kk) * 2));
+// Stage one [64][64] bf16 tile into swizzled LDS (2 sweeps x 256
+// threads x 16 B). Source rows are `stride` elements apart.
+__device__ __forceinline__ void stage_tile64(short* dst, const short* g,
+                                             long long stride, int tid) {
+  stage_tile<ATHREADS, 2>(dst, g, stride, tid);
 }
 
-// Stage one [64][64] bf16 tile into swizzled LDS: 2 global_load_lds
-// calls x 256 threads x 16 B. Source rows are `stride` elements apart.
-__device__ __forceinline__ void stage_tile(short* dst, const short* g,
-                                           long long stride, int tid) {
+// One operand fragment from global memory, multiplied by `scale` and
+// rounded back to bf16 (Q enters every product pre-scaled by 1/sqrt(D)).
+__device__ __forceinline__ bf16x8 load_frag_scaled(const short* p,
+                                                   float scale) {
+  bf16x8 raw = *(const bf16x8*)p;
 #pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const int e = aswz((s * ATHREADS + tid) * 16) / 2;
-    const short* gp = g + (long long)(e / 64) * stride + e % 64;
-    short* lp = dst + (s * ATHREADS + (tid & ~63)) * 8;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)gp,
-        (__attribute__((address_space(3))) unsigned int*)lp, 16, 0, 0);
-  }
+  for (int j = 0; j < 8; ++j) raw[j] = f2bf(bf2f(raw[j]) * scale);
+  return raw;
+}
+
+// Swizzled 2 B store of element `elem` of a [64][64] LDS tile.
+__device__ __forceinline__ void lds_st16(short* base, int elem,
+                                         short v) {
+  *(short*)((char*)base + tile_swz128(elem * 2)) = v;
 }
 
 // Variable-length batches (VARLEN): a block whose whole tile lies in the
@@ -220,22 +206,16 @@ __global__ __launch_bounds__(ATHREADS) void attn_fwd_k(
   const int lane = tid & 63;
   const int wave = tid >> 6;
 
-  const int frag_row = lane % 16;
-  const int frag_k = (lane / 16) * 8;
-  const int c_sub_row = (lane / 16) * 4;
-  const int c_col = lane % 16;
+  const FragLane fl(lane);
 
   const float qscale = rsqrtf((float)D);
   bf16x8 qf[2];
   {
-    const int qrow = qt * BQ + wave * 16 + frag_row;
+    const int qrow = qt * BQ + wave * 16 + fl.frag_row;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 raw = *(const bf16x8*)(Q + base + (long long)qrow * rs +
-                                    ks * 32 + frag_k);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) raw[j] = f2bf(bf2f(raw[j]) * qscale);
-      qf[ks] = raw;
+      qf[ks] = load_frag_scaled(
+          Q + base + (long long)qrow * rs + ks * 32 + fl.frag_k, qscale);
     }
   }
 
@@ -251,17 +231,17 @@ __global__ __launch_bounds__(ATHREADS) void attn_fwd_k(
 
   // VARLEN: only the tiles that hold a valid key (each holds >= 1)
   const int ntiles = VARLEN ? (len + BKV - 1) / BKV : S / BKV;
-  stage_tile(lK[0], K + base, rs, tid);
-  stage_tile(lVt[0], vtb, S, tid);
+  stage_tile64(lK[0], K + base, rs, tid);
+  stage_tile64(lVt[0], vtb, S, tid);
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
 
   for (int t = 0; t < ntiles; ++t) {
     const int cur = t & 1;
     if (t + 1 < ntiles) {  // prefetch next K/Vt under this tile's math
-      stage_tile(lK[cur ^ 1], K + base + (long long)(t + 1) * BKV * rs,
-                 rs, tid);
-      stage_tile(lVt[cur ^ 1], vtb + (t + 1) * BKV, S, tid);
+      stage_tile64(lK[cur ^ 1], K + base + (long long)(t + 1) * BKV * rs,
+                   rs, tid);
+      stage_tile64(lVt[cur ^ 1], vtb + (t + 1) * BKV, S, tid);
     }
 
     f32x4 s_acc[4];
@@ -270,8 +250,10 @@ __global__ __launch_bounds__(ATHREADS) void attn_fwd_k(
       s_acc[kf] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 bf = lds_ld128(lK[cur], kf * 16 + frag_row,
-                                    ks * 32 + frag_k);
+        const bf16x8 bf = lds_frag(lK[cur], kf * 16 + fl.frag_row,
+                                   ks * 32 + fl.frag_k);
+        // the builtin, not mfma_bf16: through the wrapper the compiler
+        // schedules the fixed-length instantiation differently
         s_acc[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             qf[ks], bf, s_acc[kf], 0, 0, 0);
       }
@@ -285,7 +267,7 @@ __global__ __launch_bounds__(ATHREADS) void attn_fwd_k(
       for (int kf = 0; kf < 4; ++kf)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (kf * 16 + c_col >= kvalid) s_acc[kf][r] = -1e30f;
+          if (kf * 16 + fl.c_col >= kvalid) s_acc[kf][r] = -1e30f;
     }
 
     float pmax[4];
@@ -303,15 +285,15 @@ __global__ __launch_bounds__(ATHREADS) void attn_fwd_k(
     for (int r = 0; r < 4; ++r) {
       const float m_new = fmaxf(m_run[r], pmax[r]);
       const float scale = __expf(m_run[r] - m_new);
-      const int qrow = qt * BQ + wave * 16 + c_sub_row + r;
+      const int qrow = qt * BQ + wave * 16 + fl.c_sub_row + r;
       float rowsum = 0.f;
 #pragma unroll
       for (int kf = 0; kf < 4; ++kf) {
         float p = __expf(s_acc[kf][r] - m_new);
-        if constexpr (VARLEN) p = kf * 16 + c_col < kvalid ? p : 0.f;
+        if constexpr (VARLEN) p = kf * 16 + fl.c_col < kvalid ? p : 0.f;
         rowsum += p;  // l accumulates the UNdropped probabilities
         const float keep = drop_keep(seed, bh, qrow,
-                                     t * BKV + kf * 16 + c_col, S, p24,
+                                     t * BKV + kf * 16 + fl.c_col, S, p24,
                                      inv1mp);
         s_acc[kf][r] = p * keep;  // dropped P feeds the PV product
       }
@@ -328,19 +310,18 @@ __global__ __launch_bounds__(ATHREADS) void attn_fwd_k(
     for (int kf = 0; kf < 4; ++kf)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        lds_st16(lP, (wave * 16 + c_sub_row + r) * BKV + kf * 16 + c_col,
+        lds_st16(lP, (wave * 16 + fl.c_sub_row + r) * BKV + kf * 16 + fl.c_col,
                  f2bf(s_acc[kf][r]));
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int df = 0; df < 4; ++df) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 af = lds_ld128(lP, wave * 16 + frag_row,
-                                    ks * 32 + frag_k);
-        const bf16x8 bf = lds_ld128(lVt[cur], df * 16 + frag_row,
-                                    ks * 32 + frag_k);
-        o_acc[df] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            af, bf, o_acc[df], 0, 0, 0);
+        const bf16x8 af = lds_frag(lP, wave * 16 + fl.frag_row,
+                                   ks * 32 + fl.frag_k);
+        const bf16x8 bf = lds_frag(lVt[cur], df * 16 + fl.frag_row,
+                                   ks * 32 + fl.frag_k);
+        o_acc[df] = mfma_bf16(af, bf, o_acc[df]);
       }
     }
     __builtin_amdgcn_s_setprio(0);
@@ -353,23 +334,23 @@ __global__ __launch_bounds__(ATHREADS) void attn_fwd_k(
   for (int df = 0; df < 4; ++df)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int qrow = qrow0 + c_sub_row + r;
+      const int qrow = qrow0 + fl.c_sub_row + r;
       if constexpr (VARLEN)  // tail Q tile: padded rows store zero
-        O[obase + (long long)qrow * ors + df * 16 + c_col] =
+        O[obase + (long long)qrow * ors + df * 16 + fl.c_col] =
             qrow < len ? f2bf(o_acc[df][r] / l_run[r]) : (short)0;
       else
-        O[obase + (long long)qrow * ors + df * 16 + c_col] =
+        O[obase + (long long)qrow * ors + df * 16 + fl.c_col] =
             f2bf(o_acc[df][r] / l_run[r]);
     }
-  if (LSE && c_col == 0) {
+  if (LSE && fl.c_col == 0) {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if constexpr (VARLEN)
-        LSE[(long long)bh * S + qrow0 + c_sub_row + r] =
-            qrow0 + c_sub_row + r < len ? m_run[r] + __logf(l_run[r])
+        LSE[(long long)bh * S + qrow0 + fl.c_sub_row + r] =
+            qrow0 + fl.c_sub_row + r < len ? m_run[r] + __logf(l_run[r])
                                         : 0.f;
       else
-        LSE[(long long)bh * S + qrow0 + c_sub_row + r] =
+        LSE[(long long)bh * S + qrow0 + fl.c_sub_row + r] =
             m_run[r] + __logf(l_run[r]);
   }
 }
@@ -416,6 +397,8 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dkdv_k(
   const int lane = tid & 63;
   const int wave = tid >> 6;  // owns keys [wave*16, +16)
 
+  // FragLane's four coordinates as plain locals: through the struct the
+  // compiler schedules the VARLEN instantiation differently
   const int frag_row = lane % 16;
   const int frag_k = (lane / 16) * 8;
   const int c_sub_row = (lane / 16) * 4;
@@ -442,11 +425,11 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dkdv_k(
   }
 
   auto stage_q = [&](int buf, int it) {
-    stage_tile(lQ[buf], Q + base + (long long)it * BQ * rs, rs, tid);
-    stage_tile(lQt[buf], qtb + it * BQ, S, tid);
-    stage_tile(ldO[buf], dO + obase + (long long)it * BQ * ors, ors,
-               tid);
-    stage_tile(ldOt[buf], dtb + it * BQ, S, tid);
+    stage_tile64(lQ[buf], Q + base + (long long)it * BQ * rs, rs, tid);
+    stage_tile64(lQt[buf], qtb + it * BQ, S, tid);
+    stage_tile64(ldO[buf], dO + obase + (long long)it * BQ * ors, ors,
+                 tid);
+    stage_tile64(ldOt[buf], dtb + it * BQ, S, tid);
   };
 
   // VARLEN: Q tiles beyond the length contribute nothing
@@ -467,14 +450,12 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dkdv_k(
       dpt[qf] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 bq = lds_ld128(lQ[cur], qf * 16 + frag_row,
-                                    ks * 32 + frag_k);
-        const bf16x8 bd = lds_ld128(ldO[cur], qf * 16 + frag_row,
-                                    ks * 32 + frag_k);
-        st[qf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr[ks], bq,
-                                                         st[qf], 0, 0, 0);
-        dpt[qf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            vfr[ks], bd, dpt[qf], 0, 0, 0);
+        const bf16x8 bq = lds_frag(lQ[cur], qf * 16 + frag_row,
+                                   ks * 32 + frag_k);
+        const bf16x8 bd = lds_frag(ldO[cur], qf * 16 + frag_row,
+                                   ks * 32 + frag_k);
+        st[qf] = mfma_bf16(kfr[ks], bq, st[qf]);
+        dpt[qf] = mfma_bf16(vfr[ks], bd, dpt[qf]);
       }
     }
 
@@ -509,12 +490,11 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dkdv_k(
     for (int df = 0; df < 4; ++df)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 af = lds_ld128(lT, wave * 16 + frag_row,
-                                    ks * 32 + frag_k);
-        const bf16x8 bf = lds_ld128(ldOt[cur], df * 16 + frag_row,
-                                    ks * 32 + frag_k);
-        dv[df] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, dv[df],
-                                                         0, 0, 0);
+        const bf16x8 af = lds_frag(lT, wave * 16 + frag_row,
+                                   ks * 32 + frag_k);
+        const bf16x8 bf = lds_frag(ldOt[cur], df * 16 + frag_row,
+                                   ks * 32 + frag_k);
+        dv[df] = mfma_bf16(af, bf, dv[df]);
       }
     __builtin_amdgcn_s_setprio(0);
     // overwrite lT with dS^T (own-wave rows; same-wave LDS ops are
@@ -532,12 +512,11 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dkdv_k(
     for (int df = 0; df < 4; ++df)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 af = lds_ld128(lT, wave * 16 + frag_row,
-                                    ks * 32 + frag_k);
-        const bf16x8 bf = lds_ld128(lQt[cur], df * 16 + frag_row,
-                                    ks * 32 + frag_k);
-        dk[df] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, dk[df],
-                                                         0, 0, 0);
+        const bf16x8 af = lds_frag(lT, wave * 16 + frag_row,
+                                   ks * 32 + frag_k);
+        const bf16x8 bf = lds_frag(lQt[cur], df * 16 + frag_row,
+                                   ks * 32 + frag_k);
+        dk[df] = mfma_bf16(af, bf, dk[df]);
       }
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_s_waitcnt(0);
@@ -600,30 +579,24 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dq_k(
   const int lane = tid & 63;
   const int wave = tid >> 6;
 
-  const int frag_row = lane % 16;
-  const int frag_k = (lane / 16) * 8;
-  const int c_sub_row = (lane / 16) * 4;
-  const int c_col = lane % 16;
+  const FragLane fl(lane);
   const float qscale = rsqrtf((float)D);
 
   bf16x8 qf[2], dof[2];
   {
-    const int qrow = qt * BQ + wave * 16 + frag_row;
+    const int qrow = qt * BQ + wave * 16 + fl.frag_row;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 raw = *(const bf16x8*)(Q + base + (long long)qrow * rs +
-                                    ks * 32 + frag_k);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) raw[j] = f2bf(bf2f(raw[j]) * qscale);
-      qf[ks] = raw;
+      qf[ks] = load_frag_scaled(
+          Q + base + (long long)qrow * rs + ks * 32 + fl.frag_k, qscale);
       dof[ks] = *(const bf16x8*)(dO + obase + (long long)qrow * ors +
-                                 ks * 32 + frag_k);
+                                 ks * 32 + fl.frag_k);
     }
   }
   float lse[4], di[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int q = qt * BQ + wave * 16 + c_sub_row + r;
+    const int q = qt * BQ + wave * 16 + fl.c_sub_row + r;
     lse[r] = LSE[(long long)bh * S + q];
     di[r] = Drow[(long long)bh * S + q];
   }
@@ -633,9 +606,9 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dq_k(
   for (int df = 0; df < 4; ++df) dq[df] = {0.f, 0.f, 0.f, 0.f};
 
   auto stage_kv = [&](int buf, int t) {
-    stage_tile(lK[buf], K + base + (long long)t * BKV * rs, rs, tid);
-    stage_tile(lKt[buf], ktb + t * BKV, S, tid);
-    stage_tile(lV[buf], V + base + (long long)t * BKV * rs, rs, tid);
+    stage_tile64(lK[buf], K + base + (long long)t * BKV * rs, rs, tid);
+    stage_tile64(lKt[buf], ktb + t * BKV, S, tid);
+    stage_tile64(lV[buf], V + base + (long long)t * BKV * rs, rs, tid);
   };
 
   const int ntiles = VARLEN ? (len + BKV - 1) / BKV : S / BKV;
@@ -654,14 +627,12 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dq_k(
       dp[kf] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 bk = lds_ld128(lK[cur], kf * 16 + frag_row,
-                                    ks * 32 + frag_k);
-        const bf16x8 bv = lds_ld128(lV[cur], kf * 16 + frag_row,
-                                    ks * 32 + frag_k);
-        s_acc[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            qf[ks], bk, s_acc[kf], 0, 0, 0);
-        dp[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dof[ks], bv,
-                                                         dp[kf], 0, 0, 0);
+        const bf16x8 bk = lds_frag(lK[cur], kf * 16 + fl.frag_row,
+                                   ks * 32 + fl.frag_k);
+        const bf16x8 bv = lds_frag(lV[cur], kf * 16 + fl.frag_row,
+                                   ks * 32 + fl.frag_k);
+        s_acc[kf] = mfma_bf16(qf[ks], bk, s_acc[kf]);
+        dp[kf] = mfma_bf16(dof[ks], bv, dp[kf]);
       }
     }
 
@@ -669,15 +640,15 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dq_k(
     for (int kf = 0; kf < 4; ++kf)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int q = qt * BQ + wave * 16 + c_sub_row + r;
-        const int key = t * BKV + kf * 16 + c_col;
+        const int q = qt * BQ + wave * 16 + fl.c_sub_row + r;
+        const int key = t * BKV + kf * 16 + fl.c_col;
         const float p = __expf(s_acc[kf][r] - lse[r]);
         const float keep = drop_keep(seed, bh, q, key, S, p24, inv1mp);
         float ds = p * (dp[kf][r] * keep - di[r]) * qscale;
         // padded query or key: select zero (lse/di may hold anything)
         if constexpr (VARLEN) ds = q < len && key < len ? ds : 0.f;
         lds_st16(lDS,
-                 (wave * 16 + c_sub_row + r) * BKV + kf * 16 + c_col,
+                 (wave * 16 + fl.c_sub_row + r) * BKV + kf * 16 + fl.c_col,
                  f2bf(ds));
       }
     // dQ += dS @ K (lDS rows wave-private)
@@ -686,12 +657,11 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dq_k(
     for (int df = 0; df < 4; ++df)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 af = lds_ld128(lDS, wave * 16 + frag_row,
-                                    ks * 32 + frag_k);
-        const bf16x8 bf = lds_ld128(lKt[cur], df * 16 + frag_row,
-                                    ks * 32 + frag_k);
-        dq[df] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, dq[df],
-                                                         0, 0, 0);
+        const bf16x8 af = lds_frag(lDS, wave * 16 + fl.frag_row,
+                                   ks * 32 + fl.frag_k);
+        const bf16x8 bf = lds_frag(lKt[cur], df * 16 + fl.frag_row,
+                                   ks * 32 + fl.frag_k);
+        dq[df] = mfma_bf16(af, bf, dq[df]);
       }
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_s_waitcnt(0);
@@ -703,10 +673,10 @@ __global__ __launch_bounds__(ATHREADS) void attn_bwd_dq_k(
   for (int df = 0; df < 4; ++df)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int qrow = qrow0 + c_sub_row + r;
+      const int qrow = qrow0 + fl.c_sub_row + r;
       short g = f2bf(dq[df][r]);
       if constexpr (VARLEN) g = qrow < len ? g : (short)0;
-      dQ[gbase + (long long)qrow * grs + df * 16 + c_col] = g;
+      dQ[gbase + (long long)qrow * grs + df * 16 + fl.c_col] = g;
     }
 }
 

@@ -30,12 +30,9 @@
 //     are predicated (N % 8 != 0 stores element-wise: its rows are not
 //     16-byte aligned); host requires only K % 64 == 0.
 //
-// MFMA fragment layout for mfma_f32_16x16x32_bf16 (HW-verified):
-// A-operand lane l holds A[row=l%16][k=8*(l/16)..+8]; B-operand lane l
-// holds B[k=8*(l/16)..+8][col=l%16]; C/D lane l reg r holds
-// C[row=(l/16)*4+r][col=l%16].
+// Fragment layout, swizzle, staging and fragment reads: mfma_tile.hip.h.
 
-#include "common.hip.h"
+#include "mfma_tile.hip.h"
 #include "kernels.h"
 
 namespace {
@@ -46,18 +43,8 @@ constexpr int kBK = 64;
 constexpr int kThreads = 1024;
 constexpr size_t kLds = 2 * 2 * (size_t)kBM * kBK * sizeof(short);
 
-typedef float float4x __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ float gelu_erf(float z) {
   return 0.5f * z * (1.f + erff(z * 0.70710678118654752f));
-}
-
-// st_16x32 XOR swizzle on a [row][64] bf16 tile byte offset (rows are
-// 128 B): XOR byte bits 4-6 with row bits 0-2. Involution; keeps 16 B
-// chunks intact; kills the 16-way ds_read_b128 bank conflict.
-__device__ __forceinline__ int swz(int byte_off) {
-  return byte_off ^ (((byte_off >> 7) & 7) << 4);
 }
 
 // act: 0 = identity(+bias), 1 = GELU(+bias)
@@ -68,12 +55,7 @@ __global__ __launch_bounds__(kThreads) void gemm_bias_act_k(
     short* __restrict__ Z, int M, int N, int K) {
   extern __shared__ short lds[];
 
-  // XCD-aware bijective swizzle (guide §5, m204 formula).
-  const int nwg = gridDim.x;
-  const int q = nwg / 8, r = nwg % 8;
-  const int xcd = blockIdx.x % 8, idx = blockIdx.x / 8;
-  const int wgid =
-      (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  const int wgid = xcd_remap(blockIdx.x, gridDim.x);
   const int ntn = (N + kBN - 1) / kBN;
   const long long a_row0 = (long long)(wgid / ntn) * kBM;
   const long long b_row0 = (long long)(wgid % ntn) * kBN;
@@ -83,10 +65,9 @@ __global__ __launch_bounds__(kThreads) void gemm_bias_act_k(
   const int wave = tid >> 6;
   const int wr = wave >> 2;  // 0..3 -> output rows [wr*64, +64)
   const int wc = wave & 3;   // 0..3 -> output cols [wc*64, +64)
-  const int frag_row = lane % 16;
-  const int frag_k = (lane / 16) * 8;
+  const FragLane fl(lane);
 
-  float4x acc[4][4];
+  f32x4 acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -95,30 +76,19 @@ __global__ __launch_bounds__(kThreads) void gemm_bias_act_k(
   auto bufA = [&](int b) { return lds + (size_t)b * 2 * kBM * kBK; };
   auto bufB = [&](int b) { return lds + ((size_t)b * 2 + 1) * kBM * kBK; };
 
-  // Stage one 256x64 operand tile: 2 cooperative global_load_lds calls
-  // x 1024 threads x 16 B. LDS write is linear (wave-uniform base +
-  // lane*16); the per-lane GLOBAL source is pre-permuted with the same
-  // swizzle the ds_reads apply. Rows clamp to the operand's last row.
+  // Stage one 256x64 operand tile: stage_tile<kThreads, 2> with the
+  // source rows clamped to the operand's last row.
   auto stage = [&](short* ldst, const short* g, long long row0, int k0,
                    int ld, int nrows) {
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int e_base = (s * kThreads + tid) * 8;
-      const int e = swz(e_base * 2) / 2;
-      int row = e / kBK;
-      const int kk = e % kBK;
+      const int e = tile_swz128((s * kThreads + tid) * 16) / 2;
+      const int row = e / kBK, kk = e % kBK;
       long long grow = row0 + row;
       if (grow >= nrows) grow = nrows - 1;
-      const short* gp = g + grow * (long long)ld + k0 + kk;
-      short* lp = ldst + ((s * kThreads + (tid & ~63)) * 8);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)gp,
-          (__attribute__((address_space(3))) unsigned int*)lp, 16, 0, 0);
+      global_load_lds16(g + grow * (long long)ld + k0 + kk,
+                        ldst + (s * kThreads + (tid & ~63)) * 8);
     }
-  };
-  auto ld_frag = [&](const short* ldst, int row, int kk) -> bf16x8 {
-    const int byte = swz((row * kBK + kk) * 2);
-    return *(const bf16x8*)((const char*)ldst + byte);
   };
 
   stage(bufA(0), A, a_row0, 0, K, M);
@@ -138,19 +108,18 @@ __global__ __launch_bounds__(kThreads) void gemm_bias_act_k(
       bf16x8 a[4], b[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        a[i] = ld_frag(bufA(cur), wr * 64 + i * 16 + frag_row,
-                       ks * 32 + frag_k);
+        a[i] = lds_frag(bufA(cur), wr * 64 + i * 16 + fl.frag_row,
+                        ks * 32 + fl.frag_k);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        b[j] = ld_frag(bufB(cur), wc * 64 + j * 16 + frag_row,
-                       ks * 32 + frag_k);
+        b[j] = lds_frag(bufB(cur), wc * 64 + j * 16 + fl.frag_row,
+                        ks * 32 + fl.frag_k);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a[i], b[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = mfma_bf16(a[i], b[j], acc[i][j]);
       __builtin_amdgcn_s_setprio(0);
     }
     __builtin_amdgcn_s_waitcnt(0);
@@ -158,18 +127,15 @@ __global__ __launch_bounds__(kThreads) void gemm_bias_act_k(
     cur ^= 1;
   }
 
-  // Epilogue: fp32 bias+activation per fragment
-  // (C[row=(lane/16)*4+r][col=lane%16]), then LDS-staged COALESCED
+  // Epilogue: fp32 bias+activation per C fragment, then LDS-staged COALESCED
   // writeout — the direct per-lane stores are 2-byte column scatters
   // (measured ~2x kernel time on the save-Z FFN shape); staging the
   // 256x256 bf16 tile in the now-free K-loop LDS turns the global
   // writes into row-contiguous bf16x8 stores.
-  const int c_sub_row = (lane / 16) * 4;
-  const int c_col = lane % 16;
   float bv[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const long long col = b_row0 + wc * 64 + j * 16 + c_col;
+    const long long col = b_row0 + wc * 64 + j * 16 + fl.c_col;
     bv[j] = (bias && col < N) ? bias[col] : 0.f;
   }
 
@@ -177,12 +143,12 @@ __global__ __launch_bounds__(kThreads) void gemm_bias_act_k(
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int col = wc * 64 + j * 16 + c_col;
+      const int col = wc * 64 + j * 16 + fl.c_col;
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
-          const int row = wr * 64 + i * 16 + c_sub_row + rr;
+          const int row = wr * 64 + i * 16 + fl.c_sub_row + rr;
           const float z = acc[i][j][rr] + bv[j];
           lds[row * kBN + col] =
               f2bf(!pre_act && ACT == 1 ? gelu_erf(z) : z);
@@ -264,6 +230,20 @@ __global__ __launch_bounds__(256) void transpose_bf16_k(
   }
 }
 
+// One instantiation: raise its dynamic-LDS limit on first use, launch.
+template <int ACT, bool SAVE_Z>
+void launch_gemm(int grid, hipStream_t stream, const short* A,
+                 const short* W, const float* bias, short* C, short* Z,
+                 int M, int N, int K) {
+  static const hipError_t lds_set = hipFuncSetAttribute(
+      (const void*)&gemm_bias_act_k<ACT, SAVE_Z>,
+      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
+  (void)lds_set;
+  hipLaunchKernelGGL((gemm_bias_act_k<ACT, SAVE_Z>), dim3(grid),
+                     dim3(kThreads), kLds, stream, A, W, bias, C, Z, M, N,
+                     K);
+}
+
 }  // namespace
 
 void launch_gemm_bias_act(const short* A, const short* W,
@@ -271,33 +251,12 @@ void launch_gemm_bias_act(const short* A, const short* W,
                           int N, int K, int act, hipStream_t stream) {
   const int grid =
       ((M + kBM - 1) / kBM) * ((N + kBN - 1) / kBN);
-  static bool lds_set = false;
-  if (!lds_set) {
-    (void)hipFuncSetAttribute((const void*)&gemm_bias_act_k<0, false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kLds);
-    (void)hipFuncSetAttribute((const void*)&gemm_bias_act_k<1, false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kLds);
-    (void)hipFuncSetAttribute((const void*)&gemm_bias_act_k<1, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kLds);
-    lds_set = true;
-  }
-  if (act == 1) {
-    if (Z)
-      hipLaunchKernelGGL((gemm_bias_act_k<1, true>), dim3(grid),
-                         dim3(kThreads), kLds, stream, A, W, bias, C, Z,
-                         M, N, K);
-    else
-      hipLaunchKernelGGL((gemm_bias_act_k<1, false>), dim3(grid),
-                         dim3(kThreads), kLds, stream, A, W, bias, C, Z,
-                         M, N, K);
-  } else {
-    hipLaunchKernelGGL((gemm_bias_act_k<0, false>), dim3(grid),
-                       dim3(kThreads), kLds, stream, A, W, bias, C, Z, M,
-                       N, K);
-  }
+  if (act != 1)
+    launch_gemm<0, false>(grid, stream, A, W, bias, C, Z, M, N, K);
+  else if (!Z)
+    launch_gemm<1, false>(grid, stream, A, W, bias, C, Z, M, N, K);
+  else
+    launch_gemm<1, true>(grid, stream, A, W, bias, C, Z, M, N, K);
 }
 
 void launch_transpose_bf16(const short* X, short* Y, int R, int C,

@@ -17,7 +17,7 @@
 // No bias/activation: these convs are always followed by the fused
 // BatchNormAct2d kernel.
 
-#include "common.hip.h"
+#include "mfma_tile.hip.h"
 #include "kernels.h"
 
 namespace {
@@ -26,15 +26,6 @@ constexpr int SBN = 64;        // N-block per workgroup
 constexpr int SBM = 1024;      // M rows per iteration (16 waves x 64)
 constexpr int STHREADS = 1024;
 constexpr int KMAX = 256;
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// swizzle for a [64][K] bf16 W panel: XOR byte bits 4-6 with row bits
-// 0-2 (row stride K*2 bytes, K in {64,128,256})
-__device__ __forceinline__ int swz_row(int byte_off, int row_shift) {
-  return byte_off ^ (((byte_off >> row_shift) & 7) << 4);
-}
 
 __global__ __launch_bounds__(STHREADS) void gemm_stream_k(
     const short* __restrict__ A, const short* __restrict__ W,
@@ -50,29 +41,23 @@ __global__ __launch_bounds__(STHREADS) void gemm_stream_k(
   const int nb = blockIdx.x % nnb;       // N-block
   const int widx = blockIdx.x / nnb;     // worker index within N-block
   const int nworkers = gridDim.x / nnb;
+  // the [64][K] W panel is swizzled on its K*2-byte rows, K in {64,128,256}
   const int row_shift = K == 64 ? 7 : (K == 128 ? 8 : 9);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
-  const int frag_row = lane % 16;
-  const int frag_k = (lane / 16) * 8;
-  const int c_sub_row = (lane / 16) * 4;
-  const int c_col = lane % 16;
+  const FragLane fl(lane);
 
   // stage the W panel once: 64*K elements; pre-permuted source so the
   // swizzled ds_reads see linear data
   {
     const int total = SBN * K;  // 4096..16384 elements
     for (int e0 = tid * 8; e0 < total; e0 += STHREADS * 8) {
-      const int e = swz_row(e0 * 2, row_shift) / 2;
+      const int e = tile_swz(e0 * 2, row_shift) / 2;
       const int row = e / K, kk = e % K;
-      const short* gp =
-          W + ((long long)nb * SBN + row) * K + kk;
-      short* lp = lW + (e0 - lane * 8);  // wave-uniform base
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)gp,
-          (__attribute__((address_space(3))) unsigned int*)lp, 16, 0, 0);
+      global_load_lds16(W + ((long long)nb * SBN + row) * K + kk,
+                        lW + (e0 - lane * 8));  // wave-uniform base
     }
   }
   __builtin_amdgcn_s_waitcnt(0);
@@ -93,23 +78,22 @@ __global__ __launch_bounds__(STHREADS) void gemm_stream_k(
       bf16x8 a[4], b[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        long long row = m0 + i * 16 + frag_row;
+        long long row = m0 + i * 16 + fl.frag_row;
         if (row >= M) row = M - 1;  // clamped; stores are predicated
-        a[i] = *(const bf16x8*)(A + row * K + ks * 32 + frag_k);
+        a[i] = *(const bf16x8*)(A + row * K + ks * 32 + fl.frag_k);
       }
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
+      for (int j = 0; j < 4; ++j)  // lds_frag for a K-wide row
         b[j] = *(const bf16x8*)((const char*)lW +
-                                swz_row(((j * 16 + frag_row) * K +
-                                         ks * 32 + frag_k) * 2,
-                                        row_shift));
+                                tile_swz(((j * 16 + fl.frag_row) * K +
+                                          ks * 32 + fl.frag_k) * 2,
+                                         row_shift));
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a[i], b[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = mfma_bf16(a[i], b[j], acc[i][j]);
       __builtin_amdgcn_s_setprio(0);
     }
 
@@ -123,7 +107,7 @@ __global__ __launch_bounds__(STHREADS) void gemm_stream_k(
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr)
-          myC[(c_sub_row + rr) * SBN + j * 16 + c_col] =
+          myC[(fl.c_sub_row + rr) * SBN + j * 16 + fl.c_col] =
               f2bf(acc[i][j][rr]);
       const long long gr0 = m0 + i * 16;
 #pragma unroll

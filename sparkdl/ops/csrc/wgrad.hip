@@ -10,7 +10,7 @@
 // the op ships OFF by default (SPARKDL_FUSED_WGRAD=1 opts in); probe
 // ladder in experimental/wgrad_v*.hip and profiles/wgrad_*.log.
 
-#include "common.hip.h"
+#include "mfma_tile.hip.h"
 #include "kernels.h"
 
 namespace {
@@ -20,12 +20,7 @@ constexpr int TK = 128;
 constexpr int TM = 64;
 constexpr int WTHREADS = 1024;
 
-typedef short bf16x8w __attribute__((ext_vector_type(8)));
-typedef float f32x4w __attribute__((ext_vector_type(4)));
-#define bf16x8 bf16x8w
-#define f32x4 f32x4w
-
-typedef short b16x4 __attribute__((ext_vector_type(4)));
+typedef short4v b16x4;
 
 // blocked layout: element (m, c) of a [64 m][W c] tile lives at
 //   blk_off(m, c, W) = (((m >> 2) * (W >> 4) + (c >> 4)) << 6)
@@ -79,7 +74,8 @@ __device__ __forceinline__ void lds_pin(bf16x8& v) {
 __global__ __launch_bounds__(WTHREADS) void wgrad_k(
     const short* __restrict__ dZ, const short* __restrict__ X,
     float* __restrict__ dW, long long M, int N, int K, int splits) {
-  // LDS: dzT [256 n][64 m] (32 KiB) + xT [128 k][64 m] (16 KiB), dbuf
+  // LDS: dzT [256 n][64 m] (32 KiB) + xT [128 k][64 m] (16 KiB), three
+  // buffers each (tile t computes while t+1 and t+2 are in flight)
   __shared__ short ldz[3][TN * TM];
   __shared__ short lx[3][TK * TM];
 
@@ -101,8 +97,7 @@ __global__ __launch_bounds__(WTHREADS) void wgrad_k(
   const int wave = tid >> 6;
   const int wn = wave >> 2;  // 0..3: dW rows [wn*64, +64)
   const int wk = wave & 3;   // 0..3: dW cols [wk*32, +32)
-  const int frag_row = lane % 16;
-  const int frag_k = (lane / 16) * 8;
+  const FragLane fl(lane);
 
   f32x4 acc[4][2];
 #pragma unroll
@@ -124,11 +119,8 @@ __global__ __launch_bounds__(WTHREADS) void wgrad_k(
       const int blkid = p >> 6, within = p & 63;
       const int m = (blkid / (TN >> 4)) * 4 + (within >> 4);
       const int c = (blkid % (TN >> 4)) * 16 + (within & 15);
-      const short* gp = dZ + (m0 + m) * (long long)N + n0 + c;
-      short* lp = ldz[buf] + ((s * WTHREADS + (tid & ~63)) * 8);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)gp,
-          (__attribute__((address_space(3))) unsigned int*)lp, 16, 0, 0);
+      global_load_lds16(dZ + (m0 + m) * (long long)N + n0 + c,
+                        ldz[buf] + ((s * WTHREADS + (tid & ~63)) * 8));
     }
     // X tile: 64 m x 128 k -> 1 sweep
     {
@@ -136,11 +128,8 @@ __global__ __launch_bounds__(WTHREADS) void wgrad_k(
       const int blkid = p >> 6, within = p & 63;
       const int m = (blkid / (TK >> 4)) * 4 + (within >> 4);
       const int c = (blkid % (TK >> 4)) * 16 + (within & 15);
-      const short* gp = X + (m0 + m) * (long long)K + k0 + c;
-      short* lp = lx[buf] + ((tid & ~63) * 8);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)gp,
-          (__attribute__((address_space(3))) unsigned int*)lp, 16, 0, 0);
+      global_load_lds16(X + (m0 + m) * (long long)K + k0 + c,
+                        lx[buf] + ((tid & ~63) * 8));
     }
   };
 
@@ -179,8 +168,7 @@ __global__ __launch_bounds__(WTHREADS) void wgrad_k(
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a[ks][i], b[ks][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = mfma_bf16(a[ks][i], b[ks][j], acc[i][j]);
     __builtin_amdgcn_s_setprio(0);
     // counted wait: next tile's 3 staging calls must have landed; the
     // tile-after-next's 3 calls (just issued) may stay in flight
@@ -191,16 +179,14 @@ __global__ __launch_bounds__(WTHREADS) void wgrad_k(
     __builtin_amdgcn_s_barrier();
   }
 
-  const int c_sub_row = (lane / 16) * 4;
-  const int c_col = lane % 16;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int col = k0 + wk * 32 + j * 16 + c_col;
+      const int col = k0 + wk * 32 + j * 16 + fl.c_col;
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
-        const int row = n0 + wn * 64 + i * 16 + c_sub_row + rr;
+        const int row = n0 + wn * 64 + i * 16 + fl.c_sub_row + rr;
         if (splits > 1)
           atomicAdd(&dW[(long long)row * K + col], acc[i][j][rr]);
         else
