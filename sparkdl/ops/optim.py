@@ -22,19 +22,71 @@ import sparkdl.ops as _ops
 _CHUNK = 16384  # must match kOptChunk in csrc/kernels.h
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else 0
+
+
+def _entries_key(entries):
+    """Every pointer the kernel will dereference: replacing a grad OR a
+    state tensor (load_state_dict) must rebuild the table."""
+    return tuple(tuple(_ptr(t) for t in e) for e in entries)
+
+
+def _is_dense(t):
+    """One element per memory slot, no gaps: contiguous in its own
+    memory format (channels_last conv weights are 4-D)."""
+    return (t.is_contiguous()
+            or (t.dim() == 4
+                and t.is_contiguous(memory_format=torch.channels_last))
+            or (t.dim() == 5
+                and t.is_contiguous(memory_format=torch.channels_last_3d)))
+
+
+def _validate_entries(entries, device):
+    """The kernels read p/m/v as float*, pl as bf16* and g as whichever
+    of the two pl selects, straight from raw pointers: anything else
+    would be an out-of-bounds access, so it is refused here."""
+    device = torch.device(device)
+    for ti, (p, g, m, v, pl) in enumerate(entries):
+        want = [("p", p, torch.float32), ("m", m, torch.float32)]
+        if v is not None:
+            want.append(("v", v, torch.float32))
+        if pl is not None:
+            want.append(("pl", pl, torch.bfloat16))
+        want.append(("g", g, torch.bfloat16 if pl is not None
+                     else torch.float32))
+        for name, t, dtype in want:
+            if t.dtype != dtype:
+                raise TypeError(
+                    "fused optimizer entry %d: %s is %s, the kernel needs "
+                    "%s" % (ti, name, t.dtype, dtype))
+            if not _is_dense(t):
+                raise ValueError(
+                    "fused optimizer entry %d: %s is not contiguous in "
+                    "any memory format" % (ti, name))
+            if t.device != device:
+                raise ValueError(
+                    "fused optimizer entry %d: %s is on %s, expected %s"
+                    % (ti, name, t.device, device))
+            if t.numel() != p.numel():
+                raise ValueError(
+                    "fused optimizer entry %d: %s has %d elements, p has "
+                    "%d" % (ti, name, t.numel(), p.numel()))
+
+
 class _MultiTensorTable:
     """Device-resident chunk table for one param group set."""
 
     def __init__(self, entries, device):
         # entries: list of (p_fp32_or_master, g, m, v, p_bf16_or_None).
+        _validate_entries(entries, device)
         blob = bytearray()
         bmap = []
         for ti, (p, g, m, v, pl) in enumerate(entries):
             n = p.numel()
             blob += struct.pack(
                 "<QQQQqQ", p.data_ptr(), g.data_ptr(), m.data_ptr(),
-                v.data_ptr() if v is not None else 0, n,
-                pl.data_ptr() if pl is not None else 0)
+                _ptr(v), n, _ptr(pl))
             for start in range(0, n, _CHUNK):
                 bmap.append((ti, start))
         self.chunks = torch.frombuffer(
@@ -42,12 +94,7 @@ class _MultiTensorTable:
         self.bmap = torch.tensor(
             bmap, dtype=torch.int32).flatten().to(device)
         self.nblocks = len(bmap)
-        self.key = tuple(
-            (p.data_ptr(), g.data_ptr()) for p, g, _, _, _ in entries)
-
-
-def _entries_key(entries):
-    return tuple((p.data_ptr(), g.data_ptr()) for p, g, _, _, _ in entries)
+        self.key = _entries_key(entries)
 
 
 class _FusedOptimizerMixin:
@@ -62,13 +109,45 @@ class _FusedOptimizerMixin:
                 for p in group["params"]:
                     if p.grad is not None:
                         current.append((p.data_ptr(), p.grad.data_ptr()))
-            table_key = tuple(k for t in self._tables.values()
+            table_key = tuple(k[:2] for t in self._tables.values()
                               for k in t.key)
             if tuple(current) == table_key:
                 for t in self._tables.values():
                     _ops.ext().zero_grads_(t.chunks, t.bmap, t.nblocks)
                 return
         super().zero_grad(set_to_none=set_to_none)
+
+    # fp32 optimizer state, whatever the parameter dtype
+    _FP32_STATE = ("master", "exp_avg", "exp_avg_sq", "momentum_buffer")
+
+    def load_state_dict(self, state_dict):
+        """torch casts every floating state tensor to its parameter's
+        dtype, which would leave bf16 parameters with bf16 masters and
+        moments. The fp32 state is taken from ``state_dict`` itself
+        instead, bit for bit. The chunk tables (they hold pointers to
+        the replaced state tensors) and the device step counter are
+        dropped; the next step rebuilds them from the restored state
+        and ``group["step"]``."""
+        super().load_state_dict(state_dict)
+        for saved, group in zip(state_dict["param_groups"],
+                                self.param_groups):
+            for pid, p in zip(saved["params"], group["params"]):
+                src = state_dict["state"].get(pid)
+                if src is None:
+                    continue
+                dst = self.state[p]
+                for k in self._FP32_STATE:
+                    if k in src:
+                        if src[k].dtype != torch.float32:
+                            raise TypeError(
+                                "optimizer state %r is %s in the loaded "
+                                "state_dict, expected fp32"
+                                % (k, src[k].dtype))
+                        dst[k] = src[k].detach().to(
+                            device=p.device, copy=True)
+        self._tables = {}
+        if hasattr(self, "_step_state"):
+            self._step_state = {}
 
 
 class FusedAdamW(_FusedOptimizerMixin, torch.optim.Optimizer):
