@@ -7,14 +7,18 @@ dgrad in hand-written kernels); 3x3/7x7 conv cores go through MIOpen
 (channels_last + bf16 autocast picks the implicit-GEMM MFMA paths); every
 BatchNorm/ReLU/residual-add runs through sparkdl.ops' fused bf16-NHWC
 BatchNormAct2d kernels (SURVEY.md §2.2 N4/N5 — the conv-block epilogue
-fusion); the optimizer step is sparkdl.ops.FusedSGD (one launch for all
+fusion); the stem's BatchNorm + ReLU + 3x3/2 max-pool is one kernel chain
+(sparkdl.ops.functional.batch_norm_relu_maxpool: the full-resolution
+activation, the pool indices and the full-resolution gradient are never
+written; SPARKDL_FUSED_STEM=0 composes the two modules instead, with
+bitwise the same results); the optimizer step is sparkdl.ops.FusedSGD (one launch for all
 161 tensors); gradient all-reduce is the bucketed DistributedOptimizer.
 """
 
 import torch
 import torch.nn as nn
 
-from sparkdl.ops import BatchNormAct2d, Conv1x1
+from sparkdl.ops import BatchNormAct2d, Conv1x1, batch_norm_relu_maxpool
 
 
 class Bottleneck(nn.Module):
@@ -80,7 +84,13 @@ class ResNet50(nn.Module):
                 nn.init.zeros_(m.bn3.weight)
 
     def forward(self, x):
-        x = self.stem_pool(self.stem_bn(self.stem_conv(x)))
+        # stem_bn + stem_pool as one kernel chain; the two modules stay
+        # as the owners of the parameters, buffers and pool geometry
+        bn = self.stem_bn
+        x = batch_norm_relu_maxpool(
+            self.stem_conv(x), bn.weight, bn.bias, bn.running_mean,
+            bn.running_var, momentum=bn.momentum, eps=bn.eps,
+            training=bn.training)
         x = self.stages(x)
         x = self.pool(x).flatten(1)
         return self.fc(x)

@@ -39,7 +39,8 @@ def has_ext():
 
 
 from sparkdl.ops.functional import (  # noqa: F401,E402
-    layer_norm, bias_gelu, batch_norm_act, layer_norm_ref, bias_gelu_ref,
+    layer_norm, bias_gelu, batch_norm_act, batch_norm_relu_maxpool,
+    layer_norm_ref, bias_gelu_ref,
     flash_attention, flash_attention_packed, masked_attention_ref,
     seqlens_from_mask,
 )

@@ -40,6 +40,18 @@
 //   fwd: stats (1 pass over x) -> finalize -> apply (1 pass)
 //   bwd: reduce (1 pass) -> finalize -> apply (1 pass)
 // vs MIOpen's separate BN fwd/bwd + ReLU fwd/bwd + add kernels.
+//
+// ResNet stem: BN + ReLU + MaxPool2d(3, stride 2, pad 1) as one chain
+// (bn_apply_pool_k, bn_pool_bwd_reduce_k, bn_pool_bwd_apply_k). The
+// full-resolution y, the pool's int64 indices and the full-resolution
+// dy are never written: the forward writes the pooled bf16 and one
+// byte per pooled element (the winning tap kh*3+kw, or kPoolDead where
+// the ReLU passes no gradient), and the backward kernels gather each
+// input pixel's dy from the 1, 2 or 4 windows that contain it. The
+// statistics kernels, the reduce geometry and the per-element
+// expressions (bn_affine, bn_xhat, bn_dx) are the ones of the unfused
+// chain, and the gather adds in ATen's order, so every result is
+// bitwise what bn_apply_k -> ATen max-pool (and back) gives.
 
 #include "common.hip.h"
 #include "kernels.h"
@@ -57,6 +69,20 @@ constexpr int kFoldFloats = kBlock * 2 * kVec;  // 16 KB
 // Second stage: each block finalizes kFinCh channels with
 // kBlock / kFinCh = 64 slab-row lanes per channel.
 constexpr int kFinCh = 4;
+
+// Per-element expressions, shared by the plain and the pooled kernels
+// so that both contract and round alike.
+__device__ __forceinline__ float bn_affine(short x, float scale,
+                                           float shift) {
+  return bf2f(x) * scale + shift;
+}
+__device__ __forceinline__ float bn_xhat(short x, float mean, float rstd) {
+  return (bf2f(x) - mean) * rstd;
+}
+__device__ __forceinline__ float bn_dx(float d, float xh, float k1,
+                                       float k2, float k3) {
+  return k1 * (d - k2 - xh * k3);
+}
 
 // --------------------------------------------------------------------
 // Forward
@@ -273,8 +299,8 @@ __global__ __launch_bounds__(kBlock) void bn_apply_k(
     unsigned char mbits = 0;
 #pragma unroll
     for (int j = 0; j < kVec; ++j) {
-      float f = bf2f(v[j]) * (j < 4 ? sc0[j] : sc1[j - 4]) +
-                (j < 4 ? sh0[j] : sh1[j - 4]);
+      float f = bn_affine(v[j], j < 4 ? sc0[j] : sc1[j - 4],
+                          j < 4 ? sh0[j] : sh1[j - 4]);
       if (RES) f += bf2f(res[base + j]);
       if (RELU) {
         if (f > 0.f) mbits |= (unsigned char)(1u << j);
@@ -319,7 +345,7 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_k(
         if (RELU && !(mbits & (1u << j))) d = 0.f;
         const float mean = j < 4 ? m0[j] : m1[j - 4];
         const float rstd = j < 4 ? r0[j] : r1[j - 4];
-        const float xh = (bf2f(xv[j]) - mean) * rstd;
+        const float xh = bn_xhat(xv[j], mean, rstd);
         s1[j] += d;
         s2[j] += d * xh;
       }
@@ -419,15 +445,297 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_k(
       if (RELU && !(mbits & (1u << j))) d = 0.f;
       const float mean = j < 4 ? m0[j] : m1[j - 4];
       const float rstd = j < 4 ? r0[j] : r1[j - 4];
-      const float xh = (bf2f(xv[j]) - mean) * rstd;
+      const float xh = bn_xhat(xv[j], mean, rstd);
       const float k1 = j < 4 ? a0[j] : a1[j - 4];
       const float k2 = j < 4 ? b0[j] : b1[j - 4];
       const float k3 = j < 4 ? g0[j] : g1[j - 4];
-      odx[j] = f2bf(k1 * (d - k2 - xh * k3));
+      odx[j] = f2bf(bn_dx(d, xh, k1, k2, k3));
       if (RES) odr[j] = f2bf(d);
     }
     *(short8*)(dx + base) = odx;
     if (RES) *(short8*)(dres + base) = odr;
+  }
+}
+
+// --------------------------------------------------------------------
+// BN + ReLU + MaxPool2d(3, stride 2, pad 1, floor mode), fused
+// --------------------------------------------------------------------
+// x is [N*H*W, C], the pooled tensors are [N*Ho*Wo, C] with
+// Ho = (H-1)/2 + 1, Wo = (W-1)/2 + 1. Row numbers fit 32 bits (checked
+// by the launchers), element offsets are 64-bit.
+
+typedef unsigned uint2v __attribute__((ext_vector_type(2)));
+
+// Code of a window whose maximum gets no gradient through the ReLU.
+constexpr unsigned kPoolDead = 9;
+// Never stored: what a window that does not exist is compared against.
+constexpr unsigned kPoolNone = 0xffu;
+
+struct PoolGeom {
+  int H, W, Ho, Wo;
+};
+
+// pooled = maxpool(relu(scale*x + shift)), one thread per output pixel
+// and 8 channels. Every tap is computed and rounded to bf16 as
+// bn_apply_k does before it is compared; the winner is the first
+// maximum in scan order (kh outer, kw inner, strict >, taps outside
+// the image skipped), as in ATen's NHWC kernel. code = winning tap
+// kh*3+kw, or kPoolDead where bn_apply_k would clear the winner's mask
+// bit (f > 0 is false).
+//
+// Blocks take rows in launch order, like the plain kernels. Dealing
+// each XCD a contiguous range of blocks (bn_fin_block), so that the
+// rows shared by neighbouring blocks come from one L2, measured 1-2 %
+// slower over the forward chain and over forward+backward
+// (profiles/README.md, "Round 5").
+__global__ __launch_bounds__(kBlock) void bn_apply_pool_k(
+    const short* __restrict__ x, const float* __restrict__ scale,
+    const float* __restrict__ shift, short* __restrict__ pooled,
+    unsigned char* __restrict__ code, long long orows, int cols,
+    PoolGeom g) {
+  const int tpr = cols / kVec;
+  const int rpb = kBlock / min(tpr, kBlock);
+  const int lane_col = (threadIdx.x % tpr) * kVec;
+  const int row_off = threadIdx.x / tpr;
+  if (row_off >= rpb) return;
+  const float4v sc0 = *(const float4v*)(scale + lane_col);
+  const float4v sc1 = *(const float4v*)(scale + lane_col + 4);
+  const float4v sh0 = *(const float4v*)(shift + lane_col);
+  const float4v sh1 = *(const float4v*)(shift + lane_col + 4);
+  const unsigned opix = (unsigned)(g.Ho * g.Wo);
+
+  for (long long o = (long long)blockIdx.x * rpb + row_off; o < orows;
+       o += (long long)gridDim.x * rpb) {
+    const unsigned n = (unsigned)o / opix;
+    const unsigned rem = (unsigned)o - n * opix;
+    const int oh = (int)(rem / (unsigned)g.Wo);
+    const int ow = (int)(rem - (unsigned)oh * (unsigned)g.Wo);
+    // all 9 loads issued before the first use; a tap outside the image
+    // reads the clamped (in-image) pixel and is not compared
+    short8 v[9];
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh) {
+      const int ih = min(max(2 * oh - 1 + kh, 0), g.H - 1);
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw) {
+        const int iw = min(max(2 * ow - 1 + kw, 0), g.W - 1);
+        const long long r = ((long long)n * g.H + ih) * g.W + iw;
+        v[kh * 3 + kw] = *(const short8*)(x + r * cols + lane_col);
+      }
+    }
+    float best[kVec], bestf[kVec];
+    unsigned tap[kVec];
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) {
+      best[j] = -INFINITY;
+      bestf[j] = 0.f;
+      tap[j] = 0;
+    }
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh) {
+      const int ih = 2 * oh - 1 + kh;
+      const bool hin = ih >= 0 && ih < g.H;
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw) {
+        const int iw = 2 * ow - 1 + kw;
+        const bool in = hin && iw >= 0 && iw < g.W;
+#pragma unroll
+        for (int j = 0; j < kVec; ++j) {
+          const float f =
+              bn_affine(v[kh * 3 + kw][j], j < 4 ? sc0[j] : sc1[j - 4],
+                        j < 4 ? sh0[j] : sh1[j - 4]);
+          const float q = bf2f(f2bf(fmaxf(f, 0.f)));
+          // a branch, not selects: most taps replace no maximum, and
+          // the branch-free form measured slower (stem forward chain
+          // 586 against 510 us)
+          if (in && q > best[j]) {
+            best[j] = q;
+            bestf[j] = f;
+            tap[j] = kh * 3 + kw;
+          }
+        }
+      }
+    }
+    short8 ov;
+    unsigned c0 = 0, c1 = 0;
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) {
+      union { float f; unsigned u; } b;
+      b.f = best[j];  // a bf16 value: the low half is zero
+      ov[j] = (short)(b.u >> 16);
+      const unsigned c = bestf[j] > 0.f ? tap[j] : kPoolDead;
+      if (j < 4) c0 |= c << (8 * j);
+      else c1 |= c << (8 * (j - 4));
+    }
+    const long long base = o * cols + lane_col;
+    *(short8*)(pooled + base) = ov;
+    *(uint2v*)(code + base) = uint2v{c0, c1};
+  }
+}
+
+// The pooled gradients and codes of the up to 2x2 windows that contain
+// input pixel r, loaded before any is used. Windows that do not exist
+// (even ih or iw, or past the last pooled row/column) load the first
+// window again and are given kPoolNone to match against.
+struct PoolTaps {
+  short8 dy[4];
+  uint2v code[4];
+  unsigned want[4];
+};
+
+__device__ __forceinline__ PoolTaps bn_pool_taps(
+    const short* __restrict__ dyp, const unsigned char* __restrict__ code,
+    long long r, int cols, int lane_col, const PoolGeom& g) {
+  const unsigned ipix = (unsigned)(g.H * g.W);
+  const unsigned n = (unsigned)r / ipix;
+  const unsigned rem = (unsigned)r - n * ipix;
+  const int ih = (int)(rem / (unsigned)g.W);
+  const int iw = (int)(rem - (unsigned)ih * (unsigned)g.W);
+  // window oh0 = ih/2 sees row ih as tap 1 (ih even) or 2 (ih odd); an
+  // odd row is also tap 0 of window oh0+1, if that window exists
+  const int oh0 = ih >> 1, ow0 = iw >> 1;
+  const unsigned kh0 = 1 + (ih & 1), kw0 = 1 + (iw & 1);
+  const bool h2 = (ih & 1) && oh0 + 1 < g.Ho;
+  const bool w2 = (iw & 1) && ow0 + 1 < g.Wo;
+  PoolTaps t;
+  // oh ascending, then ow ascending: ATen's order of accumulation
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const bool on = (a == 0 || h2) && (b == 0 || w2);
+      const int oh = on ? oh0 + a : oh0;
+      const int ow = on ? ow0 + b : ow0;
+      const long long base =
+          (((long long)n * g.Ho + oh) * g.Wo + ow) * cols + lane_col;
+      t.dy[a * 2 + b] = *(const short8*)(dyp + base);
+      t.code[a * 2 + b] = *(const uint2v*)(code + base);
+      t.want[a * 2 + b] =
+          on ? (a ? 0u : kh0) * 3 + (b ? 0u : kw0) : kPoolNone;
+    }
+  }
+  return t;
+}
+
+// dym of the pixel: fp32 sum of the pooled gradients whose code names
+// it, rounded to bf16, which is the dy * mask that the unfused chain
+// hands to bn_bwd_reduce_k / bn_bwd_apply_k.
+__device__ __forceinline__ void bn_pool_dym(const PoolTaps& t,
+                                            float (&d)[kVec]) {
+#pragma unroll
+  for (int j = 0; j < kVec; ++j) d[j] = 0.f;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) {
+      const unsigned c =
+          ((j < 4 ? t.code[w][0] : t.code[w][1]) >> (8 * (j & 3))) & 0xffu;
+      if (c == t.want[w]) d[j] += bf2f(t.dy[w][j]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kVec; ++j) d[j] = bf2f(f2bf(d[j]));
+}
+
+// bn_bwd_reduce_k<true, U> with dym gathered instead of loaded: same
+// grid, rows per block, unroll, fold and slab.
+template <int U>
+__global__ __launch_bounds__(kBlock) void bn_pool_bwd_reduce_k(
+    const short* __restrict__ x, const unsigned char* __restrict__ code,
+    const short* __restrict__ dyp, const float* __restrict__ save_mean,
+    const float* __restrict__ save_rstd, float* __restrict__ slab,
+    long long rows, int cols, PoolGeom g) {
+  __shared__ __attribute__((aligned(16))) float lds[kFoldFloats];
+  const int tpr = cols / kVec;
+  const int rpb = kBlock / min(tpr, kBlock);
+  const int lane_col = (threadIdx.x % tpr) * kVec;
+  const int row_off = threadIdx.x / tpr;
+
+  float s1[kVec] = {0.f}, s2[kVec] = {0.f};
+  if (row_off < rpb) {
+    const float4v m0 = *(const float4v*)(save_mean + lane_col);
+    const float4v m1 = *(const float4v*)(save_mean + lane_col + 4);
+    const float4v r0 = *(const float4v*)(save_rstd + lane_col);
+    const float4v r1 = *(const float4v*)(save_rstd + lane_col + 4);
+    auto accum = [&](const short8& xv, const PoolTaps& t) {
+      float d[kVec];
+      bn_pool_dym(t, d);
+#pragma unroll
+      for (int j = 0; j < kVec; ++j) {
+        const float mean = j < 4 ? m0[j] : m1[j - 4];
+        const float rstd = j < 4 ? r0[j] : r1[j - 4];
+        const float xh = bn_xhat(xv[j], mean, rstd);
+        s1[j] += d[j];
+        s2[j] += d[j] * xh;
+      }
+    };
+    const long long stride = (long long)gridDim.x * rpb;
+    long long r = (long long)blockIdx.x * rpb + row_off;
+    // U rows of loads issued before the first use
+    for (; r + (U - 1) * stride < rows; r += U * stride) {
+      short8 xv[U];
+      PoolTaps t[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long long ru = r + u * stride;
+        xv[u] = *(const short8*)(x + ru * cols + lane_col);
+        t[u] = bn_pool_taps(dyp, code, ru, cols, lane_col, g);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) accum(xv[u], t[u]);
+    }
+    for (; r < rows; r += stride) {
+      const short8 xv = *(const short8*)(x + r * cols + lane_col);
+      const PoolTaps t = bn_pool_taps(dyp, code, r, cols, lane_col, g);
+      accum(xv, t);
+    }
+  }
+  bn_block_fold(lds, s1, s2, rpb, row_off, lane_col, cols,
+                slab + (size_t)blockIdx.x * 2 * cols);
+}
+
+// bn_bwd_apply_k<true, false> with dym gathered instead of loaded.
+__global__ __launch_bounds__(kBlock) void bn_pool_bwd_apply_k(
+    const short* __restrict__ x, const unsigned char* __restrict__ code,
+    const short* __restrict__ dyp, const float* __restrict__ save_mean,
+    const float* __restrict__ save_rstd, const float* __restrict__ c1,
+    const float* __restrict__ c2, const float* __restrict__ c3,
+    short* __restrict__ dx, long long rows, int cols, PoolGeom g) {
+  const int tpr = cols / kVec;
+  const int rpb = kBlock / min(tpr, kBlock);
+  const int lane_col = (threadIdx.x % tpr) * kVec;
+  const int row_off = threadIdx.x / tpr;
+  if (row_off >= rpb) return;
+  const float4v m0 = *(const float4v*)(save_mean + lane_col);
+  const float4v m1 = *(const float4v*)(save_mean + lane_col + 4);
+  const float4v r0 = *(const float4v*)(save_rstd + lane_col);
+  const float4v r1 = *(const float4v*)(save_rstd + lane_col + 4);
+  const float4v a0 = *(const float4v*)(c1 + lane_col);
+  const float4v a1 = *(const float4v*)(c1 + lane_col + 4);
+  const float4v b0 = *(const float4v*)(c2 + lane_col);
+  const float4v b1 = *(const float4v*)(c2 + lane_col + 4);
+  const float4v g0 = *(const float4v*)(c3 + lane_col);
+  const float4v g1 = *(const float4v*)(c3 + lane_col + 4);
+
+  for (long long r = (long long)blockIdx.x * rpb + row_off; r < rows;
+       r += (long long)gridDim.x * rpb) {
+    const long long base = r * cols + lane_col;
+    const short8 xv = *(const short8*)(x + base);
+    const PoolTaps t = bn_pool_taps(dyp, code, r, cols, lane_col, g);
+    float d[kVec];
+    bn_pool_dym(t, d);
+    short8 odx;
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) {
+      const float mean = j < 4 ? m0[j] : m1[j - 4];
+      const float rstd = j < 4 ? r0[j] : r1[j - 4];
+      const float xh = bn_xhat(xv[j], mean, rstd);
+      const float k1 = j < 4 ? a0[j] : a1[j - 4];
+      const float k2 = j < 4 ? b0[j] : b1[j - 4];
+      const float k3 = j < 4 ? g0[j] : g1[j - 4];
+      odx[j] = f2bf(bn_dx(d[j], xh, k1, k2, k3));
+    }
+    *(short8*)(dx + base) = odx;
   }
 }
 
@@ -504,4 +812,54 @@ void launch_bn_bwd(const short* x, const unsigned char* mask,
   hipLaunchKernelGGL(ak, dim3(grid), dim3(kBlock), 0, stream, x, mask, dy,
                      save_mean, save_rstd, c1, c2, c3, dx, dres, rows,
                      cols);
+}
+
+void launch_bn_pool_fwd(const short* x, const float* gamma,
+                        const float* beta, float* running_mean,
+                        float* running_var, float* save_mean,
+                        float* save_rstd, float* scratch, short* pooled,
+                        unsigned char* code, int n, int h, int w, int cols,
+                        float momentum, float eps, bool training,
+                        hipStream_t stream) {
+  const PoolGeom g{h, w, (h - 1) / 2 + 1, (w - 1) / 2 + 1};
+  const long long rows = (long long)n * h * w;
+  const long long orows = (long long)n * g.Ho * g.Wo;
+  const int G = bn_reduce_blocks(rows, cols);
+  if (training)
+    hipLaunchKernelGGL(bn_stats_k<kUnroll>, dim3(G), dim3(kBlock), 0,
+                       stream, x, scratch, rows, cols);
+  // scratch: slab [G][2C], then scale [C], shift [C]
+  float* scale = scratch + (size_t)G * 2 * cols;
+  float* shift = scale + cols;
+  hipLaunchKernelGGL(bn_finalize_k, dim3(cols / kFinCh), dim3(kBlock), 0,
+                     stream, scratch, G, gamma, beta, running_mean,
+                     running_var, save_mean, save_rstd, scale, shift, rows,
+                     cols, momentum, eps, (int)training);
+  hipLaunchKernelGGL(bn_apply_pool_k, dim3(bn_grid(orows, cols)),
+                     dim3(kBlock), 0, stream, x, scale, shift, pooled, code,
+                     orows, cols, g);
+}
+
+void launch_bn_pool_bwd(const short* x, const unsigned char* code,
+                        const short* dyp, const float* gamma,
+                        const float* save_mean, const float* save_rstd,
+                        float* scratch, float* dgamma, float* dbeta,
+                        short* dx, int n, int h, int w, int cols,
+                        bool training, hipStream_t stream) {
+  const PoolGeom g{h, w, (h - 1) / 2 + 1, (w - 1) / 2 + 1};
+  const long long rows = (long long)n * h * w;
+  const int G = bn_reduce_blocks(rows, cols);
+  hipLaunchKernelGGL(bn_pool_bwd_reduce_k<kUnroll>, dim3(G), dim3(kBlock),
+                     0, stream, x, code, dyp, save_mean, save_rstd, scratch,
+                     rows, cols, g);
+  // scratch: slab [G][2C], then c1, c2, c3 [C] each
+  float* c1 = scratch + (size_t)G * 2 * cols;
+  float* c2 = c1 + cols;
+  float* c3 = c2 + cols;
+  hipLaunchKernelGGL(bn_bwd_finalize_k, dim3(cols / kFinCh), dim3(kBlock),
+                     0, stream, scratch, G, gamma, save_rstd, dgamma, dbeta,
+                     c1, c2, c3, rows, cols, (int)training);
+  hipLaunchKernelGGL(bn_pool_bwd_apply_k, dim3(bn_grid(rows, cols)),
+                     dim3(kBlock), 0, stream, x, code, dyp, save_mean,
+                     save_rstd, c1, c2, c3, dx, rows, cols, g);
 }

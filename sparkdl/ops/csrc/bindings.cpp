@@ -232,6 +232,91 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& x,
   return {dx, dgamma, dbeta};
 }
 
+// BatchNorm + ReLU + MaxPool2d(3, 2, 1) in one chain; x is [N,H,W,C].
+std::vector<at::Tensor> bn_pool_fwd(const at::Tensor& x,
+                                    const at::Tensor& gamma,
+                                    const at::Tensor& beta,
+                                    at::Tensor running_mean,
+                                    at::Tensor running_var, double momentum,
+                                    double eps, bool training) {
+  CHECK_BF16_CUDA(x);
+  CHECK_F32_CUDA(gamma);
+  CHECK_F32_CUDA(beta);
+  CHECK_F32_CUDA(running_mean);
+  CHECK_F32_CUDA(running_var);
+  TORCH_CHECK(x.dim() == 4, "bn_pool_fwd takes x as [N,H,W,C]");
+  DeviceGuard guard(x.device());
+  const int64_t n = x.size(0), h = x.size(1), w = x.size(2);
+  const int cols = (int)x.size(3);
+  TORCH_CHECK(cols % 8 == 0 && cols <= 2048,
+              "bn_pool_fwd requires cols%8==0 and cols<=2048");
+  TORCH_CHECK(n > 0 && h > 0 && w > 0 && n * h * w < (1LL << 31),
+              "bn_pool_fwd requires 0 < N*H*W < 2^31");
+  TORCH_CHECK(gamma.numel() == cols && beta.numel() == cols &&
+              running_mean.numel() == cols && running_var.numel() == cols);
+  const int64_t ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
+  auto f32 = x.options().dtype(at::kFloat);
+  auto pooled = at::empty({n, ho, wo, cols}, x.options());
+  auto code = at::empty({n, ho, wo, cols}, x.options().dtype(at::kByte));
+  auto save_mean = at::empty({cols}, f32);
+  auto save_rstd = at::empty({cols}, f32);
+  auto scratch = at::empty({bn_scratch_floats(n * h * w, cols)}, f32);
+  launch_bn_pool_fwd(bf_ptr(x), gamma.data_ptr<float>(),
+                     beta.data_ptr<float>(), running_mean.data_ptr<float>(),
+                     running_var.data_ptr<float>(),
+                     save_mean.data_ptr<float>(),
+                     save_rstd.data_ptr<float>(), scratch.data_ptr<float>(),
+                     bf_ptr_mut(pooled), code.data_ptr<unsigned char>(),
+                     (int)n, (int)h, (int)w, cols, (float)momentum,
+                     (float)eps, training, cur_stream());
+  return {pooled, save_mean, save_rstd, code};
+}
+
+std::vector<at::Tensor> bn_pool_bwd(const at::Tensor& x,
+                                    const at::Tensor& code,
+                                    const at::Tensor& dyp,
+                                    const at::Tensor& gamma,
+                                    const at::Tensor& save_mean,
+                                    const at::Tensor& save_rstd,
+                                    bool training) {
+  CHECK_BF16_CUDA(x);
+  CHECK_BF16_CUDA(dyp);
+  CHECK_F32_CUDA(gamma);
+  CHECK_F32_CUDA(save_mean);
+  CHECK_F32_CUDA(save_rstd);
+  TORCH_CHECK(x.dim() == 4, "bn_pool_bwd takes x as [N,H,W,C]");
+  DeviceGuard guard(x.device());
+  const int64_t n = x.size(0), h = x.size(1), w = x.size(2);
+  const int cols = (int)x.size(3);
+  TORCH_CHECK(cols % 8 == 0 && cols <= 2048,
+              "bn_pool_bwd requires cols%8==0 and cols<=2048");
+  TORCH_CHECK(n > 0 && h > 0 && w > 0 && n * h * w < (1LL << 31),
+              "bn_pool_bwd requires 0 < N*H*W < 2^31");
+  const int64_t ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
+  const std::vector<int64_t> pshape = {n, ho, wo, (int64_t)cols};
+  TORCH_CHECK(dyp.sizes() == at::IntArrayRef(pshape),
+              "pooled grad must be [N,Ho,Wo,C]");
+  TORCH_CHECK(code.is_cuda() && code.scalar_type() == at::kByte &&
+              code.is_contiguous() &&
+              code.sizes() == at::IntArrayRef(pshape),
+              "backward needs the forward's tap codes");
+  TORCH_CHECK(gamma.numel() == cols && save_mean.numel() == cols &&
+              save_rstd.numel() == cols);
+  auto f32 = x.options().dtype(at::kFloat);
+  auto dx = at::empty_like(x);
+  auto dgamma = at::empty({cols}, f32);
+  auto dbeta = at::empty({cols}, f32);
+  auto scratch = at::empty({bn_scratch_floats(n * h * w, cols)}, f32);
+  launch_bn_pool_bwd(bf_ptr(x), code.data_ptr<unsigned char>(),
+                     bf_ptr(dyp), gamma.data_ptr<float>(),
+                     save_mean.data_ptr<float>(),
+                     save_rstd.data_ptr<float>(), scratch.data_ptr<float>(),
+                     dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
+                     bf_ptr_mut(dx), (int)n, (int)h, (int)w, cols, training,
+                     cur_stream());
+  return {dx, dgamma, dbeta};
+}
+
 // ---------------------------------------------------------------------
 // Bias + GELU
 // ---------------------------------------------------------------------
@@ -576,6 +661,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gbt_histogram", &gbt_histogram, "GBT g/h histogram (N7)");
   m.def("bn_fwd", &bn_fwd, "Fused BatchNorm(+add)(+ReLU) fwd (bf16 NHWC)");
   m.def("bn_bwd", &bn_bwd, "Fused BatchNorm(+add)(+ReLU) bwd (bf16 NHWC)");
+  m.def("bn_pool_fwd", &bn_pool_fwd,
+        "Fused BatchNorm+ReLU+MaxPool(3,2,1) fwd (bf16 NHWC)");
+  m.def("bn_pool_bwd", &bn_pool_bwd,
+        "Fused BatchNorm+ReLU+MaxPool(3,2,1) bwd (bf16 NHWC)");
   m.def("layernorm_fwd", &layernorm_fwd, "LayerNorm forward (bf16)");
   m.def("layernorm_bwd", &layernorm_bwd, "LayerNorm backward (bf16)");
   m.def("bias_gelu_fwd", &bias_gelu_fwd, "Fused bias+GELU forward (bf16)");

@@ -88,6 +88,28 @@ void launch_bn_bwd(const short* x, const unsigned char* mask,
                    short* dres, long long rows, int cols, bool training,
                    bool relu, hipStream_t stream);
 
+// BatchNorm + ReLU + MaxPool2d(3, stride 2, pad 1, floor mode) as one
+// chain (the ResNet stem). x: bf16 [n, h, w, cols]; pooled, dyp and
+// code: [n, (h-1)/2+1, (w-1)/2+1, cols]. code holds one byte per pooled
+// element, the winning tap kh*3+kw or 9 where the ReLU passes no
+// gradient; it stands in for the pool's indices and the ReLU mask.
+// n*h*w must fit 31 bits. scratch as for launch_bn_fwd / launch_bn_bwd
+// at rows = n*h*w.
+void launch_bn_pool_fwd(const short* x, const float* gamma,
+                        const float* beta, float* running_mean,
+                        float* running_var, float* save_mean,
+                        float* save_rstd, float* scratch, short* pooled,
+                        unsigned char* code, int n, int h, int w, int cols,
+                        float momentum, float eps, bool training,
+                        hipStream_t stream);
+
+void launch_bn_pool_bwd(const short* x, const unsigned char* code,
+                        const short* dyp, const float* gamma,
+                        const float* save_mean, const float* save_rstd,
+                        float* scratch, float* dgamma, float* dbeta,
+                        short* dx, int n, int h, int w, int cols,
+                        bool training, hipStream_t stream);
+
 // Hand-written MFMA bf16 GEMM with fused bias(+GELU) epilogue
 // (SURVEY.md §2.2 N6): C = act(A[M,K] @ W[N,K]^T + bias), bf16 in/out,
 // fp32 accumulation; optional pre-activation save for backward.

@@ -196,6 +196,56 @@ def batch_norm_act(x, gamma, beta, running_mean, running_var,
     return torch.relu(y) if relu else y
 
 
+class _BNReLUPoolFn(torch.autograd.Function):
+    """maxpool3x3s2p1(relu(bn(x))) in one kernel chain. Besides x and
+    the statistics, backward keeps one byte per pooled element (the
+    winning tap, or "no gradient"): no full-resolution y, ReLU mask,
+    int64 pool indices or full-resolution dy exist."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum,
+                eps, training):
+        C = _ops.ext()
+        xp = _to_nhwc(x)
+        pooled, mean, rstd, code = C.bn_pool_fwd(
+            xp, gamma, beta, running_mean, running_var, momentum, eps,
+            training)
+        ctx.save_for_backward(xp, code, gamma, mean, rstd)
+        ctx.bn_training = training
+        return _from_nhwc(pooled)
+
+    @staticmethod
+    def backward(ctx, dy):
+        C = _ops.ext()
+        xp, code, gamma, mean, rstd = ctx.saved_tensors
+        dx, dgamma, dbeta = C.bn_pool_bwd(
+            xp, code, _to_nhwc(dy), gamma, mean, rstd, ctx.bn_training)
+        return _from_nhwc(dx), dgamma, dbeta, None, None, None, None, None
+
+
+def batch_norm_relu_maxpool(x, gamma, beta, running_mean, running_var,
+                            momentum=0.1, eps=1e-5, training=True):
+    """``max_pool2d(relu(batch_norm(x)), 3, stride=2, padding=1)``, the
+    ResNet stem epilogue.
+
+    bf16 GPU tensors with C % 8 == 0 and C <= 2048 run the fused CDNA4
+    kernels, whose outputs, running statistics and gradients are bitwise
+    those of the composed path; everything else (CPU included) composes
+    batch_norm_act(relu=True) with torch's max_pool2d.
+    SPARKDL_FUSED_STEM=0 forces the composed path."""
+    C = x.shape[1]
+    if (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
+            and C <= 2048 and C % 8 == 0
+            and 0 < x.numel() // C < 2 ** 31
+            and os.environ.get("SPARKDL_FUSED_STEM", "1") != "0"):
+        return _BNReLUPoolFn.apply(x, gamma, beta, running_mean,
+                                   running_var, momentum, eps, training)
+    y = batch_norm_act(x, gamma, beta, running_mean, running_var,
+                       momentum=momentum, eps=eps, training=training,
+                       relu=True)
+    return torch.nn.functional.max_pool2d(y, 3, stride=2, padding=1)
+
+
 def layer_norm(x, gamma, beta, eps=1e-5):
     """LayerNorm over the last dim. HIP kernel for bf16-on-GPU, reference
     path otherwise (CPU tests)."""
