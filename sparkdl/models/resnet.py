@@ -13,6 +13,16 @@ activation, the pool indices and the full-resolution gradient are never
 written; SPARKDL_FUSED_STEM=0 composes the two modules instead, with
 bitwise the same results); the optimizer step is sparkdl.ops.FusedSGD (one launch for all
 161 tensors); gradient all-reduce is the bucketed DistributedOptimizer.
+
+Each block's output has two consumers, the next block's conv1 and its
+residual branch (identity or down_conv). The blocks pass it on as a pair
+(BatchNormAct2d ``fork=True``), so the backward of bn3 gets the two
+gradients separately and adds them inside its reduction kernel, and the
+masked sum that kernel writes doubles as the gradient of the residual
+input: autograd's bf16 add pass and the separate residual-gradient store
+are gone at the 15 such outputs. SPARKDL_FUSED_RESGRAD=0 restores the add,
+with bitwise the same results. The stem's pooled output forks as a plain
+tensor; autograd adds there.
 """
 
 import torch
@@ -42,13 +52,19 @@ class Bottleneck(nn.Module):
             self.down_conv = None
 
     def forward(self, x):
+        """x: a tensor, or the pair a previous block returned. Returns
+        the block's output as a pair (BatchNormAct2d, ``fork=True``):
+        one member for the next block's conv1, the other for its
+        identity or down_conv, so that bn3's backward receives the two
+        gradients separately."""
+        x, skip = x if isinstance(x, tuple) else (x, x)
         if self.down_conv is not None:
-            idn = self.down_bn(self.down_conv(x))
+            idn = self.down_bn(self.down_conv(skip))
         else:
-            idn = x
+            idn = skip
         out = self.bn1(self.conv1(x))
         out = self.bn2(self.conv2(out))
-        return self.bn3(self.conv3(out), residual=idn)
+        return self.bn3(self.conv3(out), residual=idn, fork=True)
 
 
 class ResNet50(nn.Module):
@@ -91,6 +107,8 @@ class ResNet50(nn.Module):
             self.stem_conv(x), bn.weight, bn.bias, bn.running_mean,
             bn.running_var, momentum=bn.momentum, eps=bn.eps,
             training=bn.training)
-        x = self.stages(x)
+        # the last block's output has one consumer: with one member of
+        # its pair unused, its bn3 runs the one-gradient backward
+        x, _ = self.stages(x)
         x = self.pool(x).flatten(1)
         return self.fc(x)

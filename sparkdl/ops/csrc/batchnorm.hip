@@ -41,6 +41,18 @@
 //   bwd: reduce (1 pass) -> finalize -> apply (1 pass)
 // vs MIOpen's separate BN fwd/bwd + ReLU fwd/bwd + add kernels.
 //
+// Two-gradient backward (bn_bwd2_reduce_k, bn_bwd2_apply_k): where the
+// output has two consumers (a bottleneck's bn3 output feeds the next
+// block's conv1 and its residual branch), autograd would first add the
+// two incoming gradients in a pass of its own (3 tensors of traffic).
+// The reduce kernel takes both parts instead, forms
+// s = mask ? bf16(u + v) : 0 with ATen's rounding, writes s and
+// accumulates over it; the apply kernel reads x and s only. s is also
+// the gradient of the residual input, so the chain moves 7 tensors
+// where add + reduce + apply (with its dres store) moved 9. Geometry,
+// fold and per-element expressions are those of the one-gradient
+// kernels: dx, dres, dgamma and dbeta are bitwise the same.
+//
 // ResNet stem: BN + ReLU + MaxPool2d(3, stride 2, pad 1) as one chain
 // (bn_apply_pool_k, bn_pool_bwd_reduce_k, bn_pool_bwd_apply_k). The
 // full-resolution y, the pool's int64 indices and the full-resolution
@@ -458,6 +470,131 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_k(
 }
 
 // --------------------------------------------------------------------
+// Backward with two incoming gradients
+// --------------------------------------------------------------------
+// The output feeds two consumers and dy = u + v arrives as its two
+// parts. s = mask ? bf16(u + v) : 0 is the dy * mask of the chain above
+// and, rounded as ATen rounds its bf16 add, also its dres: the reduce
+// kernel writes it once, the apply kernel reads it back in place of dy
+// and the mask, and the caller hands it on as the residual gradient.
+
+// bn_bwd_reduce_k<RELU, U> over d = s: same grid, rows per block,
+// unroll, fold and slab.
+template <bool RELU, int U>
+__global__ __launch_bounds__(kBlock) void bn_bwd2_reduce_k(
+    const short* __restrict__ x, const unsigned char* __restrict__ mask,
+    const short* __restrict__ dya, const short* __restrict__ dyb,
+    const float* __restrict__ save_mean,
+    const float* __restrict__ save_rstd, short* __restrict__ s,
+    float* __restrict__ slab, long long rows, int cols) {
+  __shared__ __attribute__((aligned(16))) float lds[kFoldFloats];
+  const int tpr = cols / kVec;
+  const int rpb = kBlock / min(tpr, kBlock);
+  const int lane_col = (threadIdx.x % tpr) * kVec;
+  const int row_off = threadIdx.x / tpr;
+
+  float s1[kVec] = {0.f}, s2[kVec] = {0.f};
+  if (row_off < rpb) {
+    const float4v m0 = *(const float4v*)(save_mean + lane_col);
+    const float4v m1 = *(const float4v*)(save_mean + lane_col + 4);
+    const float4v r0 = *(const float4v*)(save_rstd + lane_col);
+    const float4v r1 = *(const float4v*)(save_rstd + lane_col + 4);
+    auto accum = [&](const short8& xv, const short8& ua, const short8& ub,
+                     unsigned char mbits, long long base) {
+      short8 sv;
+#pragma unroll
+      for (int j = 0; j < kVec; ++j) {
+        short sb = f2bf(bf2f(ua[j]) + bf2f(ub[j]));
+        if (RELU && !(mbits & (1u << j))) sb = 0;
+        sv[j] = sb;
+        const float d = bf2f(sb);
+        const float mean = j < 4 ? m0[j] : m1[j - 4];
+        const float rstd = j < 4 ? r0[j] : r1[j - 4];
+        const float xh = bn_xhat(xv[j], mean, rstd);
+        s1[j] += d;
+        s2[j] += d * xh;
+      }
+      *(short8*)(s + base) = sv;
+    };
+    const long long stride = (long long)gridDim.x * rpb;
+    long long r = (long long)blockIdx.x * rpb + row_off;
+    // U rows of loads issued before the first use
+    for (; r + (U - 1) * stride < rows; r += U * stride) {
+      short8 xv[U], ua[U], ub[U];
+      unsigned char mb[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long long base = (r + u * stride) * cols + lane_col;
+        xv[u] = *(const short8*)(x + base);
+        ua[u] = *(const short8*)(dya + base);
+        ub[u] = *(const short8*)(dyb + base);
+        mb[u] = 0xffu;
+        if (RELU) mb[u] = mask[base / kVec];
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        accum(xv[u], ua[u], ub[u], mb[u],
+              (r + u * stride) * cols + lane_col);
+    }
+    for (; r < rows; r += stride) {
+      const long long base = r * cols + lane_col;
+      const short8 xv = *(const short8*)(x + base);
+      const short8 ua = *(const short8*)(dya + base);
+      const short8 ub = *(const short8*)(dyb + base);
+      unsigned char mbits = 0xffu;
+      if (RELU) mbits = mask[base / kVec];
+      accum(xv, ua, ub, mbits, base);
+    }
+  }
+  bn_block_fold(lds, s1, s2, rpb, row_off, lane_col, cols,
+                slab + (size_t)blockIdx.x * 2 * cols);
+}
+
+// dx = c1*(s - c2 - xhat*c3): bn_bwd_apply_k on the masked sum, with no
+// mask to load and no dres to store.
+__global__ __launch_bounds__(kBlock) void bn_bwd2_apply_k(
+    const short* __restrict__ x, const short* __restrict__ s,
+    const float* __restrict__ save_mean,
+    const float* __restrict__ save_rstd, const float* __restrict__ c1,
+    const float* __restrict__ c2, const float* __restrict__ c3,
+    short* __restrict__ dx, long long rows, int cols) {
+  const int tpr = cols / kVec;
+  const int rpb = kBlock / min(tpr, kBlock);
+  const int lane_col = (threadIdx.x % tpr) * kVec;
+  const int row_off = threadIdx.x / tpr;
+  if (row_off >= rpb) return;
+  const float4v m0 = *(const float4v*)(save_mean + lane_col);
+  const float4v m1 = *(const float4v*)(save_mean + lane_col + 4);
+  const float4v r0 = *(const float4v*)(save_rstd + lane_col);
+  const float4v r1 = *(const float4v*)(save_rstd + lane_col + 4);
+  const float4v a0 = *(const float4v*)(c1 + lane_col);
+  const float4v a1 = *(const float4v*)(c1 + lane_col + 4);
+  const float4v b0 = *(const float4v*)(c2 + lane_col);
+  const float4v b1 = *(const float4v*)(c2 + lane_col + 4);
+  const float4v g0 = *(const float4v*)(c3 + lane_col);
+  const float4v g1 = *(const float4v*)(c3 + lane_col + 4);
+
+  for (long long r = (long long)blockIdx.x * rpb + row_off; r < rows;
+       r += (long long)gridDim.x * rpb) {
+    const long long base = r * cols + lane_col;
+    const short8 xv = *(const short8*)(x + base);
+    const short8 sv = *(const short8*)(s + base);
+    short8 odx;
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) {
+      const float mean = j < 4 ? m0[j] : m1[j - 4];
+      const float rstd = j < 4 ? r0[j] : r1[j - 4];
+      const float xh = bn_xhat(xv[j], mean, rstd);
+      const float k1 = j < 4 ? a0[j] : a1[j - 4];
+      const float k2 = j < 4 ? b0[j] : b1[j - 4];
+      const float k3 = j < 4 ? g0[j] : g1[j - 4];
+      odx[j] = f2bf(bn_dx(bf2f(sv[j]), xh, k1, k2, k3));
+    }
+    *(short8*)(dx + base) = odx;
+  }
+}
+
+// --------------------------------------------------------------------
 // BN + ReLU + MaxPool2d(3, stride 2, pad 1, floor mode), fused
 // --------------------------------------------------------------------
 // x is [N*H*W, C], the pooled tensors are [N*Ho*Wo, C] with
@@ -811,6 +948,30 @@ void launch_bn_bwd(const short* x, const unsigned char* mask,
                          : bn_bwd_apply_k<false, false>);
   hipLaunchKernelGGL(ak, dim3(grid), dim3(kBlock), 0, stream, x, mask, dy,
                      save_mean, save_rstd, c1, c2, c3, dx, dres, rows,
+                     cols);
+}
+
+void launch_bn_bwd2(const short* x, const unsigned char* mask,
+                    const short* dya, const short* dyb, const float* gamma,
+                    const float* save_mean, const float* save_rstd,
+                    float* scratch, float* dgamma, float* dbeta, short* dx,
+                    short* s, long long rows, int cols, bool training,
+                    bool relu, hipStream_t stream) {
+  const int grid = bn_grid(rows, cols);
+  const int G = bn_reduce_blocks(rows, cols);
+  auto rk = relu ? bn_bwd2_reduce_k<true, kUnroll>
+                 : bn_bwd2_reduce_k<false, kUnroll>;
+  hipLaunchKernelGGL(rk, dim3(G), dim3(kBlock), 0, stream, x, mask, dya,
+                     dyb, save_mean, save_rstd, s, scratch, rows, cols);
+  // scratch: slab [G][2C], then c1, c2, c3 [C] each
+  float* c1 = scratch + (size_t)G * 2 * cols;
+  float* c2 = c1 + cols;
+  float* c3 = c2 + cols;
+  hipLaunchKernelGGL(bn_bwd_finalize_k, dim3(cols / kFinCh), dim3(kBlock),
+                     0, stream, scratch, G, gamma, save_rstd, dgamma, dbeta,
+                     c1, c2, c3, rows, cols, (int)training);
+  hipLaunchKernelGGL(bn_bwd2_apply_k, dim3(grid), dim3(kBlock), 0, stream,
+                     x, s, save_mean, save_rstd, c1, c2, c3, dx, rows,
                      cols);
 }
 

@@ -232,6 +232,48 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& x,
   return {dx, dgamma, dbeta};
 }
 
+// bn_bwd for an output that had two consumers: dy = dy_a + dy_b is
+// formed inside the reduce kernel. Returns dx, dgamma, dbeta and
+// s = dy * mask, the gradient of the forward's residual input.
+std::vector<at::Tensor> bn_bwd2(const at::Tensor& x,
+                                const at::Tensor& mask,
+                                const at::Tensor& dy_a,
+                                const at::Tensor& dy_b,
+                                const at::Tensor& gamma,
+                                const at::Tensor& save_mean,
+                                const at::Tensor& save_rstd, bool training,
+                                bool relu) {
+  CHECK_BF16_CUDA(x);
+  CHECK_BF16_CUDA(dy_a);
+  CHECK_BF16_CUDA(dy_b);
+  CHECK_F32_CUDA(gamma);
+  TORCH_CHECK(dy_a.sizes() == x.sizes() && dy_b.sizes() == x.sizes(),
+              "bn_bwd2: both gradients must have x's shape");
+  DeviceGuard guard(x.device());
+  const int cols = (int)x.size(-1);
+  const long long rows = x.numel() / cols;
+  TORCH_CHECK(cols % 8 == 0 && cols <= 2048,
+              "bn_bwd2 requires cols%8==0 and cols<=2048 (NHWC channels)");
+  TORCH_CHECK(!relu || mask.numel() == rows * cols / 8,
+              "relu backward needs the forward's activation mask");
+  TORCH_CHECK(gamma.numel() == cols && save_mean.numel() == cols &&
+              save_rstd.numel() == cols);
+  auto f32 = x.options().dtype(at::kFloat);
+  auto dx = at::empty_like(x);
+  auto s = at::empty_like(x);
+  auto dgamma = at::empty({cols}, f32);
+  auto dbeta = at::empty({cols}, f32);
+  auto scratch = at::empty({bn_scratch_floats(rows, cols)}, f32);
+  launch_bn_bwd2(bf_ptr(x),
+                 relu ? mask.data_ptr<unsigned char>() : nullptr,
+                 bf_ptr(dy_a), bf_ptr(dy_b), gamma.data_ptr<float>(),
+                 save_mean.data_ptr<float>(), save_rstd.data_ptr<float>(),
+                 scratch.data_ptr<float>(), dgamma.data_ptr<float>(),
+                 dbeta.data_ptr<float>(), bf_ptr_mut(dx), bf_ptr_mut(s),
+                 rows, cols, training, relu, cur_stream());
+  return {dx, dgamma, dbeta, s};
+}
+
 // BatchNorm + ReLU + MaxPool2d(3, 2, 1) in one chain; x is [N,H,W,C].
 std::vector<at::Tensor> bn_pool_fwd(const at::Tensor& x,
                                     const at::Tensor& gamma,
@@ -661,6 +703,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gbt_histogram", &gbt_histogram, "GBT g/h histogram (N7)");
   m.def("bn_fwd", &bn_fwd, "Fused BatchNorm(+add)(+ReLU) fwd (bf16 NHWC)");
   m.def("bn_bwd", &bn_bwd, "Fused BatchNorm(+add)(+ReLU) bwd (bf16 NHWC)");
+  m.def("bn_bwd2", &bn_bwd2,
+        "Fused BatchNorm(+add)(+ReLU) bwd over the sum of two gradients");
   m.def("bn_pool_fwd", &bn_pool_fwd,
         "Fused BatchNorm+ReLU+MaxPool(3,2,1) fwd (bf16 NHWC)");
   m.def("bn_pool_bwd", &bn_pool_bwd,

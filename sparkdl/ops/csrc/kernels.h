@@ -88,6 +88,16 @@ void launch_bn_bwd(const short* x, const unsigned char* mask,
                    short* dres, long long rows, int cols, bool training,
                    bool relu, hipStream_t stream);
 
+// launch_bn_bwd for dy = dya + dyb (ATen's bf16 add), the output having
+// had two consumers. s, [rows, cols] bf16, receives dy * mask: it is
+// what launch_bn_bwd writes to dres, and is always written.
+void launch_bn_bwd2(const short* x, const unsigned char* mask,
+                    const short* dya, const short* dyb, const float* gamma,
+                    const float* save_mean, const float* save_rstd,
+                    float* scratch, float* dgamma, float* dbeta, short* dx,
+                    short* s, long long rows, int cols, bool training,
+                    bool relu, hipStream_t stream);
+
 // BatchNorm + ReLU + MaxPool2d(3, stride 2, pad 1, floor mode) as one
 // chain (the ResNet stem). x: bf16 [n, h, w, cols]; pooled, dyp and
 // code: [n, (h-1)/2+1, (w-1)/2+1, cols]. code holds one byte per pooled

@@ -141,10 +141,23 @@ def _from_nhwc(t):
     return t.permute(0, 3, 1, 2)
 
 
+def _alias(t):
+    """A tensor over t's memory, shape and strides that is no view of
+    t to autograd."""
+    return torch.empty(0, dtype=t.dtype, device=t.device).set_(
+        t.untyped_storage(), t.storage_offset(), t.size(), t.stride())
+
+
 class _BNReLUFn(torch.autograd.Function):
+    """With ``fork`` the node has two outputs, one tensor under two
+    handles for two consumers, and so receives their gradients apart:
+    the two-gradient kernels add them inside the reduction instead of
+    autograd adding them in a pass of its own, and the masked sum they
+    write is also the residual's gradient."""
+
     @staticmethod
     def forward(ctx, x, residual, gamma, beta, running_mean, running_var,
-                momentum, eps, training, relu):
+                momentum, eps, training, relu, fork=False):
         C = _ops.ext()
         xp = _to_nhwc(x)
         rp = _to_nhwc(residual) if residual is not None else None
@@ -155,29 +168,56 @@ class _BNReLUFn(torch.autograd.Function):
         # be kept alive by autograd
         ctx.save_for_backward(xp, mask, gamma, mean, rstd)
         ctx.bn_flags = (training, relu, residual is not None)
-        return _from_nhwc(y)
+        out = _from_nhwc(y)
+        if not fork:
+            return out
+        # an output a consumer leaves unused arrives as None
+        ctx.set_materialize_grads(False)
+        # two handles on y's memory, each a tensor of its own: an
+        # autograd view of one output would hand its gradient to that
+        # output instead of to this node
+        return _alias(out), _alias(out)
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, dy2=None):
         C = _ops.ext()
         xp, mask, gamma, mean, rstd = ctx.saved_tensors
         training, relu, has_res = ctx.bn_flags
         needs_dres = has_res and ctx.needs_input_grad[1]
-        outs = C.bn_bwd(xp, mask, _to_nhwc(dy), gamma, mean, rstd,
-                        training, relu, needs_dres)
+        if dy is None:
+            dy, dy2 = dy2, None
+        if dy is None:
+            return (None,) * 11
+        if dy2 is not None:
+            outs = C.bn_bwd2(xp, mask, _to_nhwc(dy), _to_nhwc(dy2), gamma,
+                             mean, rstd, training, relu)
+        else:
+            outs = C.bn_bwd(xp, mask, _to_nhwc(dy), gamma, mean, rstd,
+                            training, relu, needs_dres)
         dx = _from_nhwc(outs[0])
         dres = _from_nhwc(outs[3]) if needs_dres else None
         return (dx, dres, outs[1], outs[2], None, None, None, None, None,
-                None)
+                None, None)
 
 
 def batch_norm_act(x, gamma, beta, running_mean, running_var,
                    momentum=0.1, eps=1e-5, training=True, relu=False,
-                   residual=None):
+                   residual=None, fork=False):
     """Fused BatchNorm(+residual add)(+ReLU).
 
     bf16 channels_last GPU tensors hit the CDNA4 kernels; everything else
-    runs the reference torch path (same math, also the numerics oracle)."""
+    runs the reference torch path (same math, also the numerics oracle).
+
+    ``fork=True`` is for an output with two consumers (a bottleneck's
+    output feeds the next block's first convolution and its residual
+    branch) and returns a pair, one member for each. On the kernel path
+    the two are one tensor under two handles, so the backward gets the
+    consumers' gradients separately and sums them inside its reduction
+    kernel (bn_bwd2) instead of autograd adding them first; results are
+    bitwise the same. A consumer that leaves its member unused costs
+    nothing: one gradient runs the one-gradient kernels. On the
+    reference path, and with SPARKDL_FUSED_RESGRAD=0 on the kernel path
+    too, the pair is ``(y, y)`` and autograd adds as usual."""
     # The NHWC kernels stage per-channel folds in LDS sized for
     # C <= 2048 (csrc/batchnorm.hip `lds[kFoldFloats]`) and read bf16 in
     # 8-wide packs; larger or ragged channel counts take the reference
@@ -185,15 +225,22 @@ def batch_norm_act(x, gamma, beta, running_mean, running_var,
     C = x.shape[1]
     if (x.is_cuda and x.dtype == torch.bfloat16
             and C <= 2048 and C % 8 == 0):
-        return _BNReLUFn.apply(x, residual, gamma, beta, running_mean,
-                               running_var, momentum, eps, training, relu)
+        if fork and os.environ.get("SPARKDL_FUSED_RESGRAD", "1") != "0":
+            return _BNReLUFn.apply(x, residual, gamma, beta, running_mean,
+                                   running_var, momentum, eps, training,
+                                   relu, True)
+        y = _BNReLUFn.apply(x, residual, gamma, beta, running_mean,
+                            running_var, momentum, eps, training, relu,
+                            False)
+        return (y, y) if fork else y
     # reference path: fp32 compute (stats/affine are fp32), cast back
     y = torch.nn.functional.batch_norm(
         x.float(), running_mean, running_var, gamma, beta,
         training, momentum, eps).to(x.dtype)
     if residual is not None:
         y = y + residual
-    return torch.relu(y) if relu else y
+    y = torch.relu(y) if relu else y
+    return (y, y) if fork else y
 
 
 class _BNReLUPoolFn(torch.autograd.Function):

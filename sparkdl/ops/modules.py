@@ -34,7 +34,14 @@ class BatchNormAct2d(nn.Module):
     ``y = relu?(bn(x) [+ residual])`` in ONE kernel chain (bf16 NHWC on
     GPU; reference torch path elsewhere).  fp32 affine params and running
     stats, matching torch.nn.BatchNorm2d semantics (unbiased running
-    var, momentum EMA)."""
+    var, momentum EMA).
+
+    ``forward(x, residual, fork=True)`` returns a pair for an output
+    that has two consumers, one member for each: on the kernel path
+    the backward then takes the two gradients separately and adds them
+    inside its reduction kernel, which saves autograd's own add pass
+    and the separate store of the residual gradient (see
+    ``functional.batch_norm_act``). Elsewhere the pair is ``(y, y)``."""
 
     def __init__(self, num_features, eps=1e-5, momentum=0.1, relu=False):
         super().__init__()
@@ -51,11 +58,11 @@ class BatchNormAct2d(nn.Module):
         self.register_buffer(
             "running_var", torch.ones(num_features, dtype=torch.float32))
 
-    def forward(self, x, residual=None):
+    def forward(self, x, residual=None, fork=False):
         return F_.batch_norm_act(
             x, self.weight, self.bias, self.running_mean, self.running_var,
             momentum=self.momentum, eps=self.eps, training=self.training,
-            relu=self.relu, residual=residual)
+            relu=self.relu, residual=residual, fork=fork)
 
     def extra_repr(self):
         return "%d, relu=%s" % (self.num_features, self.relu)
