@@ -9,9 +9,18 @@ in-kernel dropout) — no Triton/aotriton and no library GEMM on the
 fwd/dgrad path (wgrad remains hipBLASLt, see NOTES-round2.md);
 LayerNorm and the optimizer (fused multi-tensor AdamW) are hand-written
 CDNA4 kernels.
+
+The two sublayer tails of every layer, ``ln(x + drop(sublayer(x)))``,
+are eager dropout and add in front of the LayerNorm kernel by default.
+``BertConfig(fused_dropout_ln=True)`` (or SPARKDL_FUSED_DROPOUT_LN=1)
+runs each as one kernel forward and one backward
+(``ops.dropout_add_layer_norm``) with no stored mask. It is opt-in
+because its dropout mask is the kernels' counter hash, not torch's
+Philox draw: the same seed then gives another training trajectory.
 """
 
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -21,7 +30,8 @@ from sparkdl.ops import LayerNorm, Linear, LinearGelu
 
 class BertConfig:
     def __init__(self, vocab_size=30522, hidden=768, layers=12, heads=12,
-                 ffn=3072, max_seq=512, type_vocab=2, dropout=0.1):
+                 ffn=3072, max_seq=512, type_vocab=2, dropout=0.1,
+                 fused_dropout_ln=None):
         self.vocab_size = vocab_size
         self.hidden = hidden
         self.layers = layers
@@ -30,6 +40,11 @@ class BertConfig:
         self.max_seq = max_seq
         self.type_vocab = type_vocab
         self.dropout = dropout
+        # None: SPARKDL_FUSED_DROPOUT_LN ("1" = on); off by default
+        if fused_dropout_ln is None:
+            fused_dropout_ln = os.environ.get(
+                "SPARKDL_FUSED_DROPOUT_LN", "0") == "1"
+        self.fused_dropout_ln = bool(fused_dropout_ln)
 
 
 class BertEmbeddings(nn.Module):
@@ -99,8 +114,18 @@ class BertLayer(nn.Module):
         self.ffn_out = Linear(cfg.ffn, cfg.hidden)
         self.ln2 = LayerNorm(cfg.hidden, eps=1e-12)
         self.drop = nn.Dropout(cfg.dropout)
+        self.fused_dropout_ln = getattr(cfg, "fused_dropout_ln", False)
+
+    def _tail(self, ln, sub, x):
+        """ln(x + drop(sub)) as one op, on ln's parameters."""
+        from sparkdl.ops import functional as F_
+        return F_.dropout_add_layer_norm(sub, x, ln.weight, ln.bias,
+                                         self.drop.p, self.training, ln.eps)
 
     def forward(self, x, seq_lens=None):
+        if self.fused_dropout_ln:
+            x = self._tail(self.ln1, self.attn(x, seq_lens), x)
+            return self._tail(self.ln2, self.ffn_out(self.ffn_in(x)), x)
         x = self.ln1(x + self.drop(self.attn(x, seq_lens)))
         x = self.ln2(x + self.drop(self.ffn_out(self.ffn_in(x))))
         return x

@@ -1,7 +1,7 @@
 """sparkdl.ops — hand-written CDNA4 (gfx950) kernels and their wrappers.
 
 Hot-path ops: fused multi-tensor AdamW/SGD,
-LayerNorm, fused bias+GELU.  The HIP extension (sparkdl._C) is built
+LayerNorm, dropout+add+LayerNorm, fused bias+GELU.  The HIP extension (sparkdl._C) is built
 in-tree for gfx950; on a GPU these ops REQUIRE it — a missing extension
 raises instead of silently falling back to eager PyTorch.  On CPU
 tensors the pure-PyTorch reference path runs (that reference is also
@@ -42,10 +42,10 @@ from sparkdl.ops.functional import (  # noqa: F401,E402
     layer_norm, bias_gelu, batch_norm_act, batch_norm_relu_maxpool,
     layer_norm_ref, bias_gelu_ref,
     flash_attention, flash_attention_packed, masked_attention_ref,
-    seqlens_from_mask,
+    seqlens_from_mask, dropout_add_layer_norm, dropout_keep_mask,
 )
 from sparkdl.ops.modules import (  # noqa: F401,E402
     LayerNorm, Linear, LinearGelu, Conv1x1, BatchNormAct2d,
-    convert_bf16_training,
+    DropoutAddLayerNorm, convert_bf16_training,
 )
 from sparkdl.ops.optim import FusedAdamW, FusedSGD  # noqa: F401,E402

@@ -75,16 +75,6 @@ constexpr int BKV = 64;
 constexpr int ATHREADS = 256;
 constexpr int TILE_ELEMS = 64 * 64;
 
-__device__ __forceinline__ unsigned drop_hash(unsigned seed,
-                                              unsigned idx) {
-  unsigned x = seed ^ (idx * 2654435761u);
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
 __device__ __forceinline__ float drop_keep(unsigned seed,
                                            unsigned long long bh,
                                            int q, int k, int S,

@@ -12,6 +12,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 
 #include <cmath>
+#include <utility>
 #include <vector>
 
 #include "kernels.h"
@@ -643,6 +644,113 @@ at::Tensor transpose_bf16(const at::Tensor& X) {
 }
 
 // ---------------------------------------------------------------------
+// Dropout + residual add + LayerNorm (the BERT sublayer tail)
+// ---------------------------------------------------------------------
+
+// Shared validation; returns {rows, cols}. a and b are the two bf16
+// activations of the call (sub/res forward, h/dy backward).
+static std::pair<int, int> dropout_add_ln_check(
+    const at::Tensor& a, const at::Tensor& b, const at::Tensor& gamma,
+    double p, const c10::optional<at::Tensor>& seed) {
+  TORCH_CHECK(a.dim() >= 1 && a.sizes() == b.sizes(),
+              "dropout_add_ln: activation shapes differ: ", a.sizes(),
+              " vs ", b.sizes());
+  TORCH_CHECK(b.device() == a.device() && gamma.device() == a.device(),
+              "dropout_add_ln: tensors must share one device");
+  TORCH_CHECK(a.numel() > 0 && a.numel() < (int64_t(1) << 31),
+              "dropout_add_ln: numel must be in [1, 2^31), got ",
+              a.numel());
+  const int64_t cols = a.size(-1);
+  TORCH_CHECK(gamma.numel() == cols, "dropout_add_ln: gamma has ",
+              gamma.numel(), " elements, rows have ", cols);
+  TORCH_CHECK(p >= 0.0 && (float)p < 1.f,
+              "dropout_add_ln: p must be in [0, 1), "
+              "got ", p);
+  TORCH_CHECK(p == 0.0 || seed.has_value(),
+              "dropout_add_ln: dropout needs a seed tensor");
+  if (seed.has_value())
+    TORCH_CHECK(seed->device() == a.device(),
+                "dropout_add_ln: seed must be on the data's device");
+  return {(int)(a.numel() / cols), (int)cols};
+}
+
+std::vector<at::Tensor> dropout_add_ln_fwd(
+    const at::Tensor& sub, const at::Tensor& res, const at::Tensor& gamma,
+    const at::Tensor& beta, double eps, double p,
+    const c10::optional<at::Tensor>& seed) {
+  CHECK_BF16_CUDA(sub);
+  CHECK_BF16_CUDA(res);
+  CHECK_F32_CUDA(gamma);
+  CHECK_F32_CUDA(beta);
+  const auto [rows, cols] = dropout_add_ln_check(sub, res, gamma, p, seed);
+  TORCH_CHECK(beta.numel() == cols && beta.device() == sub.device(),
+              "dropout_add_ln_fwd: beta must match gamma");
+  DeviceGuard guard(sub.device());
+
+  auto y = at::empty_like(sub);
+  auto h = at::empty_like(sub);
+  auto f32 = sub.options().dtype(at::kFloat);
+  auto mean = at::empty({rows}, f32);
+  auto rstd = at::empty({rows}, f32);
+  launch_dropout_add_ln_fwd(
+      bf_ptr(sub), bf_ptr(res), gamma.data_ptr<float>(),
+      beta.data_ptr<float>(), bf_ptr_mut(y), bf_ptr_mut(h),
+      mean.data_ptr<float>(), rstd.data_ptr<float>(), rows, cols,
+      (float)eps, (float)p, p > 0.0 ? seed_ptr(seed) : nullptr,
+      cur_stream());
+  return {y, h, mean, rstd};
+}
+
+// -> {d_sub, d_res, dgamma, dbeta}; with p == 0 d_sub IS d_res.
+std::vector<at::Tensor> dropout_add_ln_bwd(
+    const at::Tensor& h, const at::Tensor& dy, const at::Tensor& gamma,
+    const at::Tensor& mean, const at::Tensor& rstd, double p,
+    const c10::optional<at::Tensor>& seed) {
+  CHECK_BF16_CUDA(h);
+  CHECK_BF16_CUDA(dy);
+  CHECK_F32_CUDA(gamma);
+  CHECK_F32_CUDA(mean);
+  CHECK_F32_CUDA(rstd);
+  const auto [rows, cols] = dropout_add_ln_check(h, dy, gamma, p, seed);
+  TORCH_CHECK(mean.numel() == rows && rstd.numel() == rows,
+              "dropout_add_ln_bwd: mean/rstd must hold one value per row");
+  TORCH_CHECK(mean.device() == h.device() && rstd.device() == h.device(),
+              "dropout_add_ln_bwd: tensors must share one device");
+  TORCH_CHECK(cols <= 8192,
+              "dropout_add_ln_bwd LDS partials support cols<=8192");
+  DeviceGuard guard(h.device());
+
+  auto d_res = at::empty_like(h);
+  auto d_sub = p > 0.0 ? at::empty_like(h) : d_res;
+  auto f32 = h.options().dtype(at::kFloat);
+  const int blocks = layernorm_bwd_part_rows(rows);
+  const int ws_rows = blocks * 4;  // one partial row per wave
+  auto dgamma_part = at::empty({ws_rows, cols}, f32);
+  auto dbeta_part = at::empty({ws_rows, cols}, f32);
+  auto dgamma = at::zeros({cols}, f32);
+  auto dbeta = at::zeros({cols}, f32);
+  if (p > 0.0) {
+    launch_dropout_add_ln_bwd(
+        bf_ptr(h), bf_ptr(dy), gamma.data_ptr<float>(),
+        mean.data_ptr<float>(), rstd.data_ptr<float>(), bf_ptr_mut(d_res),
+        bf_ptr_mut(d_sub), dgamma_part.data_ptr<float>(),
+        dbeta_part.data_ptr<float>(), blocks, rows, cols, (float)p,
+        seed_ptr(seed), cur_stream());
+  } else {
+    launch_layernorm_bwd(bf_ptr(h), bf_ptr(dy), gamma.data_ptr<float>(),
+                         mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                         bf_ptr_mut(d_res), dgamma_part.data_ptr<float>(),
+                         dbeta_part.data_ptr<float>(), blocks, rows, cols,
+                         cur_stream());
+  }
+  launch_layernorm_reduce_parts(
+      dgamma_part.data_ptr<float>(), dbeta_part.data_ptr<float>(),
+      dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), ws_rows, cols,
+      cur_stream());
+  return {d_sub, d_res, dgamma, dbeta};
+}
+
+// ---------------------------------------------------------------------
 // GBT histogram
 // ---------------------------------------------------------------------
 
@@ -711,6 +819,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused BatchNorm+ReLU+MaxPool(3,2,1) bwd (bf16 NHWC)");
   m.def("layernorm_fwd", &layernorm_fwd, "LayerNorm forward (bf16)");
   m.def("layernorm_bwd", &layernorm_bwd, "LayerNorm backward (bf16)");
+  m.def("dropout_add_ln_fwd", &dropout_add_ln_fwd,
+        "ln(res + dropout(sub)) forward (bf16) -> y, h, mean, rstd",
+        py::arg("sub"), py::arg("res"), py::arg("gamma"), py::arg("beta"),
+        py::arg("eps"), py::arg("p"), py::arg("seed") = py::none());
+  m.def("dropout_add_ln_bwd", &dropout_add_ln_bwd,
+        "ln(res + dropout(sub)) backward -> d_sub, d_res, dgamma, dbeta",
+        py::arg("h"), py::arg("dy"), py::arg("gamma"), py::arg("mean"),
+        py::arg("rstd"), py::arg("p"), py::arg("seed") = py::none());
   m.def("bias_gelu_fwd", &bias_gelu_fwd, "Fused bias+GELU forward (bf16)");
   m.def("bias_gelu_bwd", &bias_gelu_bwd, "Fused bias+GELU backward (bf16)");
   m.attr("_chunk_elems") = kOptChunk;

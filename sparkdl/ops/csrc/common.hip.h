@@ -54,3 +54,16 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
   __syncthreads();
   return total;
 }
+
+// Counter-hash RNG behind every in-kernel dropout: 32 mixed bits for
+// element idx under seed; the low 24 are compared against p * 2^24.
+__device__ __forceinline__ unsigned drop_hash(unsigned seed,
+                                              unsigned idx) {
+  unsigned x = seed ^ (idx * 2654435761u);
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}

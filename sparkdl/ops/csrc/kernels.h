@@ -56,6 +56,32 @@ void launch_layernorm_reduce_parts(const float* dgamma_part,
                                    float* dbeta, int part_rows, int cols,
                                    hipStream_t stream);
 
+// Dropout + residual add + LayerNorm, the BERT sublayer tail
+// y = ln(h), h = bf16(res + d), d = keep ? bf16(sub * 1/(1-p)) : +0,
+// keep(row, col) = (drop_hash((unsigned)*seed, row*cols + col) &
+// 0xffffff) >= (unsigned)(p * 2^24), index in 32-bit unsigned, so
+// rows * cols < 2^31. Bitwise the bf16 dropout, bf16 add and
+// launch_layernorm_fwd composed under the same mask. The mask is not
+// stored: backward hashes it again from the same seed (device int64[1],
+// may be null when p == 0). h is saved in x's place; the backward is
+// launch_layernorm_bwd on (h, dy) with d_res = its dx, plus
+// d_sub = keep ? bf16(d_res * 1/(1-p)) : +0 written in the same pass.
+// Partials and their reduction as for launch_layernorm_bwd.
+void launch_dropout_add_ln_fwd(const short* sub, const short* res,
+                               const float* gamma, const float* beta,
+                               short* y, short* h, float* save_mean,
+                               float* save_rstd, int rows, int cols,
+                               float eps, float p, const long long* seed,
+                               hipStream_t stream);
+
+void launch_dropout_add_ln_bwd(const short* h, const short* dy,
+                               const float* gamma, const float* save_mean,
+                               const float* save_rstd, short* d_res,
+                               short* d_sub, float* dgamma_part,
+                               float* dbeta_part, int part_rows, int rows,
+                               int cols, float p, const long long* seed,
+                               hipStream_t stream);
+
 // Fused bias + GELU (erf form), bf16 activations, fp32 bias
 // (SURVEY.md §2.2 N6 epilogue).
 void launch_bias_gelu_fwd(const short* x, const float* bias, short* y,

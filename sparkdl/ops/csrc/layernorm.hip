@@ -24,24 +24,82 @@ constexpr int kBlock = 256;           // 4 waves = 4 rows per block-iter
 constexpr int kWavesPerBlock = kBlock / WAVE;
 constexpr int kVec = 8;               // bf16 elems per lane load
 
+// Dropout + residual add fused in front of the LayerNorm: the BERT
+// sublayer tail ln(res + drop(sub)). The kernels below take one of these
+// two as their last argument; NoDrop leaves them the plain LayerNorm.
+//
+//   keep(row, col) = (drop_hash(seed, row*cols + col) & 0xffffff) >= p24
+//   d = keep ? bf16(sub * inv1mp) : +0        h = bf16(res + d)
+//
+// (index in 32-bit unsigned; the bindings hold numel below 2^31). The
+// two roundings are those of a bf16 dropout followed by a bf16 add, so
+// given the mask the forward is bitwise the composed path and the
+// statistics are those of layernorm_fwd_k on h. No mask is stored:
+// backward hashes it again and writes d_sub = keep ? bf16(d_res *
+// inv1mp) : +0 beside d_res = dx.
+struct NoDrop {
+  static constexpr bool on = false;
+};
+struct Drop {
+  static constexpr bool on = true;
+  const short* res;        // forward: the residual [rows, cols]
+  short* out;              // forward: h; backward: d_sub
+  const long long* seed;   // device int64[1], low 32 bits used
+  unsigned p24;            // (unsigned)(p * 2^24); 0 keeps all
+  float inv1mp;            // 1 / (1 - p)
+};
+
+__device__ __forceinline__ bool drop_keeps(unsigned seed, unsigned idx,
+                                           unsigned p24) {
+  return (drop_hash(seed, idx) & 0xffffffu) >= p24;
+}
+
+// One element of h.
+__device__ __forceinline__ short drop_add(short sub, short res, bool keep,
+                                          float inv1mp) {
+  const short d = keep ? f2bf(bf2f(sub) * inv1mp) : (short)0;
+  return f2bf(bf2f(res) + bf2f(d));
+}
+
+// With Drop, x is the sublayer output: pass 1 forms h from it and the
+// residual, stores it and takes the statistics from the stored values;
+// pass 2 reads h back (each lane its own stores) where the plain kernel
+// reads x again.
+template <class D>
 __global__ __launch_bounds__(kBlock) void layernorm_fwd_k(
     const short* __restrict__ x, const float* __restrict__ gamma,
     const float* __restrict__ beta, short* __restrict__ y,
     float* __restrict__ save_mean, float* __restrict__ save_rstd,
-    int rows, int cols, float eps) {
+    int rows, int cols, float eps, D d) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
+  unsigned seed = 0;
+  if constexpr (D::on) seed = d.seed ? (unsigned)(*d.seed) : 0u;
 
   for (int row = blockIdx.x * kWavesPerBlock + wid; row < rows;
        row += gridDim.x * kWavesPerBlock) {
     const short* xr = x + (long long)row * cols;
     short* yr = y + (long long)row * cols;
+    if constexpr (D::on) xr = d.out + (long long)row * cols;
 
     // Pass 1: sum and sum of squares (fp32).
     float s = 0.f, ss = 0.f;
     for (int c = lane * kVec; c < cols; c += WAVE * kVec) {
       if (c + kVec <= cols) {
-        const short8 v = *(const short8*)(xr + c);
+        short8 v;
+        if constexpr (D::on) {
+          const long long at = (long long)row * cols + c;
+          const short8 sv = *(const short8*)(x + at);
+          const short8 rv = *(const short8*)(d.res + at);
+#pragma unroll
+          for (int j = 0; j < kVec; ++j)
+            v[j] = drop_add(sv[j], rv[j],
+                            drop_keeps(seed, (unsigned)at + j, d.p24),
+                            d.inv1mp);
+          *(short8*)(d.out + at) = v;
+        } else {
+          v = *(const short8*)(xr + c);
+        }
 #pragma unroll
         for (int j = 0; j < kVec; ++j) {
           const float f = bf2f(v[j]);
@@ -50,7 +108,16 @@ __global__ __launch_bounds__(kBlock) void layernorm_fwd_k(
         }
       } else {
         for (int cc = c; cc < cols; ++cc) {
-          const float f = bf2f(xr[cc]);
+          short hv;
+          if constexpr (D::on) {
+            const long long at = (long long)row * cols + cc;
+            hv = drop_add(x[at], d.res[at],
+                          drop_keeps(seed, (unsigned)at, d.p24), d.inv1mp);
+            d.out[at] = hv;
+          } else {
+            hv = xr[cc];
+          }
+          const float f = bf2f(hv);
           s += f;
           ss += f * f;
         }
@@ -90,6 +157,34 @@ __global__ __launch_bounds__(kBlock) void layernorm_fwd_k(
   }
 }
 
+// d_sub beside a dx store: the dropout's backward on the rounded dx.
+__device__ __forceinline__ short drop_grad(short dx, bool keep,
+                                           float inv1mp) {
+  return keep ? f2bf(bf2f(dx) * inv1mp) : (short)0;
+}
+
+__device__ __forceinline__ void drop_grad_store8(const Drop& d,
+                                                 unsigned seed, int row,
+                                                 int cols, int c,
+                                                 const short8& dx) {
+  const long long at = (long long)row * cols + c;
+  short8 o;
+#pragma unroll
+  for (int j = 0; j < kVec; ++j)
+    o[j] = drop_grad(dx[j], drop_keeps(seed, (unsigned)at + j, d.p24),
+                     d.inv1mp);
+  *(short8*)(d.out + at) = o;
+}
+
+__device__ __forceinline__ void drop_grad_store1(const Drop& d,
+                                                 unsigned seed, int row,
+                                                 int cols, int cc,
+                                                 short dx) {
+  const long long at = (long long)row * cols + cc;
+  d.out[at] = drop_grad(dx, drop_keeps(seed, (unsigned)at, d.p24),
+                        d.inv1mp);
+}
+
 // dx = rstd * (dyg - mean(dyg) - xhat * mean(dyg * xhat)),  dyg = dy*gamma
 //
 // dgamma/dbeta partials accumulate in REGISTERS per thread (static
@@ -99,15 +194,19 @@ __global__ __launch_bounds__(kBlock) void layernorm_fwd_k(
 // partial row of the workspace at the end; no LDS and no atomics on the
 // hot path.  KMAX is a template parameter dispatched on cols (<=2048);
 // wider rows fall back to the LDS-atomic variant.
-template <int KMAX>
+//
+// With Drop, x is h and each dx store is followed by the d_sub store.
+template <int KMAX, class D>
 __global__ __launch_bounds__(kBlock) void layernorm_bwd_reg_k(
     const short* __restrict__ x, const short* __restrict__ dy,
     const float* __restrict__ gamma, const float* __restrict__ save_mean,
     const float* __restrict__ save_rstd, short* __restrict__ dx,
     float* __restrict__ dgamma_part, float* __restrict__ dbeta_part,
-    int rows, int cols) {
+    int rows, int cols, D d) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
+  unsigned seed = 0;
+  if constexpr (D::on) seed = d.seed ? (unsigned)(*d.seed) : 0u;
 
   float dg[KMAX][kVec], db[KMAX][kVec];
 #pragma unroll
@@ -176,11 +275,14 @@ __global__ __launch_bounds__(kBlock) void layernorm_bwd_reg_k(
           o[j] = f2bf(rstd * (dyg - s1 - xh * s2));
         }
         *(short8*)(dxr + c) = o;
+        if constexpr (D::on) drop_grad_store8(d, seed, row, cols, c, o);
       } else if (c < cols) {
         for (int cc = c; cc < cols; ++cc) {
           const float xh = (bf2f(xr[cc]) - mean) * rstd;
           const float dyg = bf2f(dyr[cc]) * gamma[cc];
-          dxr[cc] = f2bf(rstd * (dyg - s1 - xh * s2));
+          const short o = f2bf(rstd * (dyg - s1 - xh * s2));
+          dxr[cc] = o;
+          if constexpr (D::on) drop_grad_store1(d, seed, row, cols, cc, o);
         }
       }
     }
@@ -212,14 +314,17 @@ __global__ __launch_bounds__(kBlock) void layernorm_bwd_reg_k(
 // LDS-atomic fallback for cols > 2048 (up to 8192).
 extern __shared__ float ln_lds[];
 
+template <class D>
 __global__ __launch_bounds__(kBlock) void layernorm_bwd_k(
     const short* __restrict__ x, const short* __restrict__ dy,
     const float* __restrict__ gamma, const float* __restrict__ save_mean,
     const float* __restrict__ save_rstd, short* __restrict__ dx,
     float* __restrict__ dgamma_part, float* __restrict__ dbeta_part,
-    int rows, int cols) {
+    int rows, int cols, D d) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
+  unsigned seed = 0;
+  if constexpr (D::on) seed = d.seed ? (unsigned)(*d.seed) : 0u;
   float* dg_l = ln_lds;          // [cols]
   float* db_l = ln_lds + cols;   // [cols]
 
@@ -279,11 +384,14 @@ __global__ __launch_bounds__(kBlock) void layernorm_bwd_k(
           o[j] = f2bf(rstd * (dyg - s1 - xh * s2));
         }
         *(short8*)(dxr + c) = o;
+        if constexpr (D::on) drop_grad_store8(d, seed, row, cols, c, o);
       } else {
         for (int cc = c; cc < cols; ++cc) {
           const float xh = (bf2f(xr[cc]) - mean) * rstd;
           const float dyg = bf2f(dyr[cc]) * gamma[cc];
-          dxr[cc] = f2bf(rstd * (dyg - s1 - xh * s2));
+          const short o = f2bf(rstd * (dyg - s1 - xh * s2));
+          dxr[cc] = o;
+          if constexpr (D::on) drop_grad_store1(d, seed, row, cols, cc, o);
         }
       }
     }
@@ -336,13 +444,64 @@ int layernorm_bwd_part_rows(int rows) {
   return min(blocks, 512);
 }
 
+static Drop drop_args(const short* res, short* out, const long long* seed,
+                      float p) {
+  // p24 and inv1mp as launch_attn_fwd forms them
+  return Drop{res, out, seed, (unsigned)(p * 16777216.0f),
+              p > 0.f ? 1.f / (1.f - p) : 1.f};
+}
+
 void launch_layernorm_fwd(const short* x, const float* gamma,
                           const float* beta, short* y, float* save_mean,
                           float* save_rstd, int rows, int cols, float eps,
                           hipStream_t stream) {
-  hipLaunchKernelGGL(layernorm_fwd_k, dim3(ln_grid(rows)), dim3(kBlock), 0,
-                     stream, x, gamma, beta, y, save_mean, save_rstd, rows,
-                     cols, eps);
+  hipLaunchKernelGGL(layernorm_fwd_k<NoDrop>, dim3(ln_grid(rows)),
+                     dim3(kBlock), 0, stream, x, gamma, beta, y, save_mean,
+                     save_rstd, rows, cols, eps, NoDrop{});
+}
+
+void launch_dropout_add_ln_fwd(const short* sub, const short* res,
+                               const float* gamma, const float* beta,
+                               short* y, short* h, float* save_mean,
+                               float* save_rstd, int rows, int cols,
+                               float eps, float p, const long long* seed,
+                               hipStream_t stream) {
+  hipLaunchKernelGGL(layernorm_fwd_k<Drop>, dim3(ln_grid(rows)),
+                     dim3(kBlock), 0, stream, sub, gamma, beta, y,
+                     save_mean, save_rstd, rows, cols, eps,
+                     drop_args(res, h, seed, p));
+}
+
+template <class D>
+static void ln_bwd_dispatch(const short* x, const short* dy,
+                            const float* gamma, const float* save_mean,
+                            const float* save_rstd, short* dx,
+                            float* dgamma_part, float* dbeta_part,
+                            int blocks, int rows, int cols, D d,
+                            hipStream_t stream) {
+  // workspace has blocks * kWavesPerBlock partial rows (one per wave)
+  const int kmax = (cols + WAVE * kVec - 1) / (WAVE * kVec);
+  if (kmax == 1) {
+    hipLaunchKernelGGL((layernorm_bwd_reg_k<1, D>), dim3(blocks),
+                       dim3(kBlock), 0, stream, x, dy, gamma, save_mean,
+                       save_rstd, dx, dgamma_part, dbeta_part, rows, cols,
+                       d);
+  } else if (kmax == 2) {
+    hipLaunchKernelGGL((layernorm_bwd_reg_k<2, D>), dim3(blocks),
+                       dim3(kBlock), 0, stream, x, dy, gamma, save_mean,
+                       save_rstd, dx, dgamma_part, dbeta_part, rows, cols,
+                       d);
+  } else if (kmax <= 4) {
+    hipLaunchKernelGGL((layernorm_bwd_reg_k<4, D>), dim3(blocks),
+                       dim3(kBlock), 0, stream, x, dy, gamma, save_mean,
+                       save_rstd, dx, dgamma_part, dbeta_part, rows, cols,
+                       d);
+  } else {
+    const size_t lds = 2 * (size_t)cols * sizeof(float);
+    hipLaunchKernelGGL(layernorm_bwd_k<D>, dim3(blocks), dim3(kBlock), lds,
+                       stream, x, dy, gamma, save_mean, save_rstd, dx,
+                       dgamma_part, dbeta_part, rows, cols, d);
+  }
 }
 
 void launch_layernorm_bwd(const short* x, const short* dy,
@@ -351,26 +510,20 @@ void launch_layernorm_bwd(const short* x, const short* dy,
                           float* dgamma_part, float* dbeta_part,
                           int blocks, int rows, int cols,
                           hipStream_t stream) {
-  // workspace has blocks * kWavesPerBlock partial rows (one per wave)
-  const int kmax = (cols + WAVE * kVec - 1) / (WAVE * kVec);
-  if (kmax == 1) {
-    hipLaunchKernelGGL(layernorm_bwd_reg_k<1>, dim3(blocks), dim3(kBlock),
-                       0, stream, x, dy, gamma, save_mean, save_rstd, dx,
-                       dgamma_part, dbeta_part, rows, cols);
-  } else if (kmax == 2) {
-    hipLaunchKernelGGL(layernorm_bwd_reg_k<2>, dim3(blocks), dim3(kBlock),
-                       0, stream, x, dy, gamma, save_mean, save_rstd, dx,
-                       dgamma_part, dbeta_part, rows, cols);
-  } else if (kmax <= 4) {
-    hipLaunchKernelGGL(layernorm_bwd_reg_k<4>, dim3(blocks), dim3(kBlock),
-                       0, stream, x, dy, gamma, save_mean, save_rstd, dx,
-                       dgamma_part, dbeta_part, rows, cols);
-  } else {
-    const size_t lds = 2 * (size_t)cols * sizeof(float);
-    hipLaunchKernelGGL(layernorm_bwd_k, dim3(blocks), dim3(kBlock), lds,
-                       stream, x, dy, gamma, save_mean, save_rstd, dx,
-                       dgamma_part, dbeta_part, rows, cols);
-  }
+  ln_bwd_dispatch(x, dy, gamma, save_mean, save_rstd, dx, dgamma_part,
+                  dbeta_part, blocks, rows, cols, NoDrop{}, stream);
+}
+
+void launch_dropout_add_ln_bwd(const short* h, const short* dy,
+                               const float* gamma, const float* save_mean,
+                               const float* save_rstd, short* d_res,
+                               short* d_sub, float* dgamma_part,
+                               float* dbeta_part, int blocks, int rows,
+                               int cols, float p, const long long* seed,
+                               hipStream_t stream) {
+  ln_bwd_dispatch(h, dy, gamma, save_mean, save_rstd, d_res, dgamma_part,
+                  dbeta_part, blocks, rows, cols,
+                  drop_args(nullptr, d_sub, seed, p), stream);
 }
 
 void launch_layernorm_reduce_parts(const float* dgamma_part,

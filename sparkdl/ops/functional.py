@@ -302,6 +302,114 @@ def layer_norm(x, gamma, beta, eps=1e-5):
         x, (x.shape[-1],), gamma.to(x.dtype), beta.to(x.dtype), eps)
 
 
+def _mul32(x, c):
+    """x * c mod 2^32 on int64 tensors holding 32-bit values, without
+    leaving the int64 range."""
+    lo = x * (c & 0xffff)
+    hi = (x * (c >> 16)) & 0xffff
+    return (lo + (hi << 16)) & 0xffffffff
+
+
+def dropout_keep_mask(seed, rows, cols, p, device="cpu"):
+    """The keep mask of the dropout_add_layer_norm kernels as a bool
+    ``[rows, cols]`` tensor, in integer torch ops. This is the kernels'
+    specification: forward and backward regenerate exactly this mask
+    from the seed and store none.
+
+    ``seed`` (an int or a one-element integer tensor) is truncated to
+    its low 32 bits, and the element index ``i = row * cols + col`` is
+    a 32-bit unsigned number (``rows * cols < 2^31``)::
+
+        x = seed ^ (i * 2654435761)        all mod 2^32
+        x ^= x >> 16;  x *= 0x7feb352d
+        x ^= x >> 15;  x *= 0x846ca68b
+        x ^= x >> 16
+        keep = (x & 0xffffff) >= p24,  p24 = int(float32(p) * 2^24)
+
+    so ``p24 == 0`` keeps everything and an element is kept with
+    probability ``1 - p24 / 2^24``. It is the counter hash (drop_hash
+    in csrc/common.hip.h) that the attention kernels use for
+    attention-probability dropout."""
+    if not 0 <= rows * cols < 2 ** 31:
+        raise ValueError("rows * cols must be below 2^31")
+    if not 0.0 <= p < 1.0:
+        raise ValueError("p must be in [0, 1), got %r" % (p,))
+    seed = int(seed) & 0xffffffff
+    p24 = int(torch.tensor(p, dtype=torch.float32).item() * 16777216.0)
+    i = torch.arange(rows * cols, dtype=torch.int64, device=device)
+    x = _mul32(i, 2654435761) ^ seed
+    x = _mul32(x ^ (x >> 16), 0x7feb352d)
+    x = _mul32(x ^ (x >> 15), 0x846ca68b)
+    x = x ^ (x >> 16)
+    return ((x & 0xffffff) >= p24).view(rows, cols)
+
+
+class _DropoutAddLayerNormFn(torch.autograd.Function):
+    """y = ln(h), h = residual + dropout(x), through dropout_add_ln_fwd
+    / _bwd. Saves h and the statistics; the mask is regenerated from
+    the step's seed."""
+
+    @staticmethod
+    def forward(ctx, x, residual, gamma, beta, p, eps):
+        C = _ops.ext()
+        seed = None
+        if p > 0:
+            # the attention kernels' counter: advanced on the device, so
+            # a captured graph advances it on replay, and cloned so that
+            # backward replays this step's mask
+            seed = _attn_seed_tensor(x.device)
+            seed.add_(1)
+            seed = seed.clone()
+        y, h, mean, rstd = C.dropout_add_ln_fwd(
+            x.contiguous(), residual.contiguous(), gamma, beta, eps,
+            float(p), seed)
+        ctx.save_for_backward(h, gamma, mean, rstd,
+                              seed if seed is not None else
+                              torch.empty(0))
+        ctx.dropout_p = float(p)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        C = _ops.ext()
+        h, gamma, mean, rstd, seed = ctx.saved_tensors
+        if seed.numel() == 0:
+            seed = None
+        d_sub, d_res, dgamma, dbeta = C.dropout_add_ln_bwd(
+            h, dy.contiguous(), gamma, mean, rstd, ctx.dropout_p, seed)
+        return d_sub, d_res, dgamma, dbeta, None, None
+
+
+def dropout_add_layer_norm(x, residual, gamma, beta, p=0.0, training=True,
+                           eps=1e-5):
+    """``layer_norm(residual + dropout(x, p, training))``, the tail of a
+    post-norm transformer sublayer.
+
+    bf16 GPU tensors of one shape with ``p < 1``, at most 8192 columns
+    and fewer than 2^31 elements run one HIP kernel forward and one
+    backward (csrc/layernorm.hip): no dropped tensor, no sum and no mask
+    travel through memory in between, and no mask is kept for backward.
+    The mask is ``dropout_keep_mask`` under the per-device seed counter
+    that attention dropout uses (it advances by one per training call
+    with ``p > 0``); given that mask, outputs and gradients are bitwise
+    those of bf16 dropout, bf16 add and ``layer_norm`` composed. The
+    mask is not torch's: the same ``torch.manual_seed`` gives another
+    draw than the composed path.
+
+    Everything else (CPU, fp32, ``p == 1``, wider rows) runs the
+    composed path on torch's dropout."""
+    cols = x.shape[-1] if x.dim() else 0
+    if (x.is_cuda and x.dtype == torch.bfloat16
+            and residual.is_cuda and residual.dtype == torch.bfloat16
+            and residual.shape == x.shape and p < 1
+            and cols <= 8192 and 0 < x.numel() < 2 ** 31):
+        return _DropoutAddLayerNormFn.apply(
+            x, residual, gamma, beta, p if training else 0.0, eps)
+    return layer_norm(
+        residual + torch.nn.functional.dropout(x, p, training),
+        gamma, beta, eps)
+
+
 def bias_gelu(x, bias):
     """Fused bias+GELU (erf). HIP kernel for bf16-on-GPU, reference path
     otherwise."""

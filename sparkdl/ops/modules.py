@@ -29,6 +29,30 @@ class LayerNorm(nn.Module):
         return "%d, eps=%g" % (self.weight.numel(), self.eps)
 
 
+class DropoutAddLayerNorm(nn.Module):
+    """``forward(x, residual) = layer_norm(residual + dropout(x))``, the
+    tail of a post-norm transformer sublayer as one op
+    (``functional.dropout_add_layer_norm``: one HIP kernel each way for
+    bf16 on the GPU, the composed torch path elsewhere). fp32 ``weight``
+    and ``bias`` like ``LayerNorm``; the dropout is active in training
+    mode only."""
+
+    def __init__(self, hidden, p=0.1, eps=1e-5):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(hidden, dtype=torch.float32))
+        self.bias = nn.Parameter(torch.zeros(hidden, dtype=torch.float32))
+        self.p = p
+        self.eps = eps
+
+    def forward(self, x, residual):
+        return F_.dropout_add_layer_norm(x, residual, self.weight,
+                                         self.bias, self.p, self.training,
+                                         self.eps)
+
+    def extra_repr(self):
+        return "%d, p=%g, eps=%g" % (self.weight.numel(), self.p, self.eps)
+
+
 class BatchNormAct2d(nn.Module):
     """Fused BatchNorm2d with optional ReLU and residual add:
     ``y = relu?(bn(x) [+ residual])`` in ONE kernel chain (bf16 NHWC on
