@@ -1,10 +1,20 @@
 """ResNet-50 for the flagship images/sec benchmark (BASELINE.json
 configs 2-3), written from scratch.
 
-MI355X mapping: the bottleneck 1x1 convolutions run on the in-house
-256x256 MFMA GEMM over NHWC rows (sparkdl.ops.Conv1x1 — forward and
-dgrad in hand-written kernels); 3x3/7x7 conv cores go through MIOpen
-(channels_last + bf16 autocast picks the implicit-GEMM MFMA paths); every
+MI355X mapping: convolutions go through MIOpen (channels_last + bf16
+autocast picks the implicit-GEMM MFMA paths) under the committed tuning,
+except the forward of the stride-1 1x1 convolutions with Cin <= 256
+(conv1/bn1, conv3/bn3 and the first stage's down_conv/down_bn, called
+through sparkdl.ops.functional.conv1x1_bn_act): in training mode it runs
+the in-house conv1x1_stats kernel, which reads the input once and writes
+the BatchNorm partial sums in its epilogue, so the BatchNorm that follows
+skips its statistics pass over the convolution output. Which sites take
+it is functional.CONV1X1_STATS_SITES, decided site by site by
+scripts/probe_conv1x1_bn.py (profiles/probe_conv1x1_bn.log,
+profiles/README.md "Round 7"); their dgrad and wgrad stay on MIOpen, and
+SPARKDL_CONV1X1_STATS=0 restores the unfused route exactly. The all
+in-house 1x1 package (sparkdl.ops.Conv1x1 with SPARKDL_CONV1X1=1/all)
+stays opt-in. Every
 BatchNorm/ReLU/residual-add runs through sparkdl.ops' fused bf16-NHWC
 BatchNormAct2d kernels (SURVEY.md §2.2 N4/N5 — the conv-block epilogue
 fusion); the stem's BatchNorm + ReLU + 3x3/2 max-pool is one kernel chain
@@ -28,7 +38,8 @@ tensor; autograd adds there.
 import torch
 import torch.nn as nn
 
-from sparkdl.ops import BatchNormAct2d, Conv1x1, batch_norm_relu_maxpool
+from sparkdl.ops import (BatchNormAct2d, Conv1x1, batch_norm_relu_maxpool,
+                         conv1x1_bn_act)
 
 
 class Bottleneck(nn.Module):
@@ -59,12 +70,13 @@ class Bottleneck(nn.Module):
         gradients separately."""
         x, skip = x if isinstance(x, tuple) else (x, x)
         if self.down_conv is not None:
-            idn = self.down_bn(self.down_conv(skip))
+            idn = conv1x1_bn_act(skip, self.down_conv, self.down_bn)
         else:
             idn = skip
-        out = self.bn1(self.conv1(x))
+        out = conv1x1_bn_act(x, self.conv1, self.bn1)
         out = self.bn2(self.conv2(out))
-        return self.bn3(self.conv3(out), residual=idn, fork=True)
+        return conv1x1_bn_act(out, self.conv3, self.bn3, residual=idn,
+                              fork=True)
 
 
 class ResNet50(nn.Module):

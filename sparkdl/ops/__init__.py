@@ -43,6 +43,7 @@ from sparkdl.ops.functional import (  # noqa: F401,E402
     layer_norm_ref, bias_gelu_ref,
     flash_attention, flash_attention_packed, masked_attention_ref,
     seqlens_from_mask, dropout_add_layer_norm, dropout_keep_mask,
+    conv1x1_bn_act,
 )
 from sparkdl.ops.modules import (  # noqa: F401,E402
     LayerNorm, Linear, LinearGelu, Conv1x1, BatchNormAct2d,

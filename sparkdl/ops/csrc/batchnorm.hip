@@ -923,6 +923,28 @@ void launch_bn_fwd(const short* x, const short* res, const float* gamma,
                      scale, shift, y, mask, rows, cols);
 }
 
+void launch_bn_fwd_slab(const short* x, const short* res,
+                        const float* slab, int G, const float* gamma,
+                        const float* beta, float* running_mean,
+                        float* running_var, float* save_mean,
+                        float* save_rstd, float* coef, short* y,
+                        unsigned char* mask, long long rows, int cols,
+                        float momentum, float eps, bool relu,
+                        hipStream_t stream) {
+  // the slab's G rows come from the caller's kernel; coef: scale, shift
+  float* scale = coef;
+  float* shift = coef + cols;
+  hipLaunchKernelGGL(bn_finalize_k, dim3(cols / kFinCh), dim3(kBlock), 0,
+                     stream, slab, G, gamma, beta, running_mean,
+                     running_var, save_mean, save_rstd, scale, shift, rows,
+                     cols, momentum, eps, 1);
+  auto ap = relu ? (res ? bn_apply_k<true, true> : bn_apply_k<true, false>)
+                 : (res ? bn_apply_k<false, true>
+                        : bn_apply_k<false, false>);
+  hipLaunchKernelGGL(ap, dim3(bn_grid(rows, cols)), dim3(kBlock), 0, stream,
+                     x, res, scale, shift, y, mask, rows, cols);
+}
+
 void launch_bn_bwd(const short* x, const unsigned char* mask,
                    const short* dy, const float* gamma,
                    const float* save_mean, const float* save_rstd,

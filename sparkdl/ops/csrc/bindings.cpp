@@ -196,6 +196,63 @@ std::vector<at::Tensor> bn_fwd(const at::Tensor& x,
   return {y, save_mean, save_rstd, mask};
 }
 
+// bn_fwd in training mode over a slab of partial sums [G, 2*cols] that
+// the producer of x wrote (conv1x1_stats): no statistics pass.
+std::vector<at::Tensor> bn_fwd_slab(const at::Tensor& x,
+                                    const c10::optional<at::Tensor>& res,
+                                    const at::Tensor& slab,
+                                    const at::Tensor& gamma,
+                                    const at::Tensor& beta,
+                                    at::Tensor running_mean,
+                                    at::Tensor running_var, double momentum,
+                                    double eps, bool relu) {
+  CHECK_BF16_CUDA(x);
+  CHECK_F32_CUDA(slab);
+  CHECK_F32_CUDA(gamma);
+  CHECK_F32_CUDA(beta);
+  CHECK_F32_CUDA(running_mean);
+  CHECK_F32_CUDA(running_var);
+  DeviceGuard guard(x.device());
+  const int cols = (int)x.size(-1);
+  const long long rows = x.numel() / cols;
+  TORCH_CHECK(cols % 8 == 0 && cols <= 2048,
+              "bn_fwd_slab requires cols%8==0 and cols<=2048");
+  TORCH_CHECK(slab.dim() == 2 && slab.size(0) >= 1 &&
+                  slab.size(1) == 2 * (int64_t)cols &&
+                  slab.device() == x.device(),
+              "bn_fwd_slab: slab must be [G, 2*cols] on x's device");
+  TORCH_CHECK(gamma.numel() == cols && beta.numel() == cols &&
+              running_mean.numel() == cols && running_var.numel() == cols);
+  const short* res_ptr = nullptr;
+  if (res.has_value()) {
+    CHECK_BF16_CUDA(res.value());
+    TORCH_CHECK(res->sizes() == x.sizes());
+    res_ptr = bf_ptr(res.value());
+  }
+  auto f32 = x.options().dtype(at::kFloat);
+  auto y = at::empty_like(x);
+  auto save_mean = at::empty({cols}, f32);
+  auto save_rstd = at::empty({cols}, f32);
+  auto coef = at::empty({2 * (int64_t)cols}, f32);
+  at::Tensor mask;
+  unsigned char* mask_ptr = nullptr;
+  if (relu) {
+    mask = at::empty({rows * cols / 8}, x.options().dtype(at::kByte));
+    mask_ptr = mask.data_ptr<unsigned char>();
+  } else {
+    mask = at::empty({0}, x.options().dtype(at::kByte));
+  }
+  launch_bn_fwd_slab(bf_ptr(x), res_ptr, slab.data_ptr<float>(),
+                     (int)slab.size(0), gamma.data_ptr<float>(),
+                     beta.data_ptr<float>(), running_mean.data_ptr<float>(),
+                     running_var.data_ptr<float>(),
+                     save_mean.data_ptr<float>(),
+                     save_rstd.data_ptr<float>(), coef.data_ptr<float>(),
+                     bf_ptr_mut(y), mask_ptr, rows, cols, (float)momentum,
+                     (float)eps, relu, cur_stream());
+  return {y, save_mean, save_rstd, mask};
+}
+
 std::vector<at::Tensor> bn_bwd(const at::Tensor& x,
                                const at::Tensor& mask,
                                const at::Tensor& dy,
@@ -442,6 +499,50 @@ at::Tensor gemm_stream(const at::Tensor& A, const at::Tensor& W) {
   launch_gemm_stream(bf_ptr(A), bf_ptr(W), bf_ptr_mut(C), M, N, K,
                      cur_stream());
   return C;
+}
+
+// C = A @ W^T and the BatchNorm partial sums of C, A read once.
+// Returns {C [M,N] bf16, slab [G, 2N] fp32}; a slab passed in (tests)
+// must have exactly that shape and is the one written and returned.
+std::vector<at::Tensor> conv1x1_stats(
+    const at::Tensor& A, const at::Tensor& W, int64_t max_workers,
+    const c10::optional<at::Tensor>& slab_out) {
+  CHECK_BF16_CUDA(A);
+  CHECK_BF16_CUDA(W);
+  TORCH_CHECK(A.dim() == 2 && W.dim() == 2 && A.size(1) == W.size(1));
+  TORCH_CHECK(W.device() == A.device());
+  const long long M = A.size(0);
+  const int K = (int)A.size(1), N = (int)W.size(0);
+  TORCH_CHECK(conv1x1_stats_supported(M, N, K),
+              "conv1x1_stats requires K in {64,128,256}, N % 64 == 0 and "
+              "M >= 1");
+  TORCH_CHECK(max_workers >= 0 && max_workers < (1 << 20));
+  DeviceGuard guard(A.device());
+  int nch, G;
+  conv1x1_stats_plan(M, N, K, (int)max_workers, &nch, &G);
+  auto C = at::empty({M, N}, A.options());
+  at::Tensor slab;
+  if (slab_out.has_value()) {
+    slab = slab_out.value();
+    CHECK_F32_CUDA(slab);
+    TORCH_CHECK(slab.device() == A.device() && slab.dim() == 2 &&
+                    slab.size(0) == G && slab.size(1) == 2 * (int64_t)N,
+                "conv1x1_stats: slab must be [", G, ", ", 2 * N, "]");
+  } else {
+    slab = at::empty({G, 2 * (int64_t)N}, A.options().dtype(at::kFloat));
+  }
+  launch_conv1x1_stats(bf_ptr(A), bf_ptr(W), bf_ptr_mut(C),
+                       slab.data_ptr<float>(), M, N, K, (int)max_workers,
+                       cur_stream());
+  return {C, slab};
+}
+
+std::vector<int64_t> conv1x1_stats_plan_py(int64_t M, int64_t N, int64_t K,
+                                           int64_t max_workers) {
+  TORCH_CHECK(conv1x1_stats_supported(M, (int)N, (int)K));
+  int nch, G;
+  conv1x1_stats_plan(M, (int)N, (int)K, (int)max_workers, &nch, &G);
+  return {nch, G};
 }
 
 // ---------------------------------------------------------------------
@@ -788,6 +889,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transpose_bf16", &transpose_bf16, "bf16 2D transpose (dgrad W^T)");
   m.def("gemm_stream", &gemm_stream,
         "Streaming tall-skinny GEMM (1x1 convs)");
+  m.def("conv1x1_stats", &conv1x1_stats,
+        "Read-once 1x1 conv forward + BatchNorm partial sums -> C, slab",
+        py::arg("a"), py::arg("w"), py::arg("max_workers") = 0,
+        py::arg("slab") = py::none());
+  m.def("conv1x1_stats_plan", &conv1x1_stats_plan_py,
+        "(chunks per N-block, slab rows G) of a conv1x1_stats launch",
+        py::arg("m"), py::arg("n"), py::arg("k"),
+        py::arg("max_workers") = 0);
+  m.def("bn_fwd_slab", &bn_fwd_slab,
+        "Fused BatchNorm(+add)(+ReLU) fwd over pre-summed statistics");
   m.def("wgrad_splitk", &wgrad_splitk,
         "Split-M wgrad GEMM (tr_b16 fragment path)");
   // trailing seqlens defaults to None, so the five-/six-/eight-argument

@@ -107,6 +107,20 @@ void launch_bn_fwd(const short* x, const short* res, const float* gamma,
                    long long rows, int cols, float momentum, float eps,
                    bool training, bool relu, hipStream_t stream);
 
+// launch_bn_fwd in training mode over statistics that the producer of x
+// already summed: slab is fp32 [G][2*cols] in bn_stats_k's layout (per
+// row [0..cols) sums, [cols..2*cols) sums of squares of x's bf16
+// values), every row written. bn_stats_k is skipped; bn_finalize_k and
+// bn_apply_k run unchanged. coef: fp32[2*cols], uninitialized.
+void launch_bn_fwd_slab(const short* x, const short* res,
+                        const float* slab, int G, const float* gamma,
+                        const float* beta, float* running_mean,
+                        float* running_var, float* save_mean,
+                        float* save_rstd, float* coef, short* y,
+                        unsigned char* mask, long long rows, int cols,
+                        float momentum, float eps, bool relu,
+                        hipStream_t stream);
+
 void launch_bn_bwd(const short* x, const unsigned char* mask,
                    const short* dy, const float* gamma,
                    const float* save_mean, const float* save_rstd,
@@ -160,6 +174,18 @@ bool gemm_bias_act_supported(int M, int N, int K);
 void launch_gemm_stream(const short* A, const short* W, short* C,
                         long long M, int N, int K, hipStream_t stream);
 bool gemm_stream_supported(long long M, int N, int K);
+
+// Read-once 1x1 convolution forward with BatchNorm partial sums
+// (csrc/conv1x1_stats.hip): C = A @ W^T as launch_gemm_stream, plus the
+// fp32 slab [G][2*N] of launch_bn_fwd_slab over the stored bf16 C.
+// conv1x1_stats_plan gives the slab rows G (and the 64-column chunks
+// per N-block) of a launch; max_workers > 0 caps G.
+bool conv1x1_stats_supported(long long M, int N, int K);
+void conv1x1_stats_plan(long long M, int N, int K, int max_workers,
+                        int* nch, int* G);
+void launch_conv1x1_stats(const short* A, const short* W, short* C,
+                          float* slab, long long M, int N, int K,
+                          int max_workers, hipStream_t stream);
 
 // Split-M wgrad GEMM (dW = dZ^T @ X, M-major operands): blocked-LDS
 // tr_b16 fragment path, fp32 output with split atomics. Ships behind

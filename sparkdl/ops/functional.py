@@ -153,17 +153,26 @@ class _BNReLUFn(torch.autograd.Function):
     handles for two consumers, and so receives their gradients apart:
     the two-gradient kernels add them inside the reduction instead of
     autograd adding them in a pass of its own, and the masked sum they
-    write is also the residual's gradient."""
+    write is also the residual's gradient.
+
+    ``slab`` (training only): the partial sums of x that its producer
+    already wrote (``_Conv1x1StatsFn``); the statistics pass over x is
+    then skipped. It gets no gradient."""
 
     @staticmethod
     def forward(ctx, x, residual, gamma, beta, running_mean, running_var,
-                momentum, eps, training, relu, fork=False):
+                momentum, eps, training, relu, fork=False, slab=None):
         C = _ops.ext()
         xp = _to_nhwc(x)
         rp = _to_nhwc(residual) if residual is not None else None
-        y, mean, rstd, mask = C.bn_fwd(
-            xp, rp, gamma, beta, running_mean, running_var, momentum,
-            eps, training, relu)
+        if slab is not None and training:
+            y, mean, rstd, mask = C.bn_fwd_slab(
+                xp, rp, slab, gamma, beta, running_mean, running_var,
+                momentum, eps, relu)
+        else:
+            y, mean, rstd, mask = C.bn_fwd(
+                xp, rp, gamma, beta, running_mean, running_var, momentum,
+                eps, training, relu)
         # mask (1 bit/elem) replaces y in backward — y itself need not
         # be kept alive by autograd
         ctx.save_for_backward(xp, mask, gamma, mean, rstd)
@@ -187,7 +196,7 @@ class _BNReLUFn(torch.autograd.Function):
         if dy is None:
             dy, dy2 = dy2, None
         if dy is None:
-            return (None,) * 11
+            return (None,) * 12
         if dy2 is not None:
             outs = C.bn_bwd2(xp, mask, _to_nhwc(dy), _to_nhwc(dy2), gamma,
                              mean, rstd, training, relu)
@@ -197,12 +206,12 @@ class _BNReLUFn(torch.autograd.Function):
         dx = _from_nhwc(outs[0])
         dres = _from_nhwc(outs[3]) if needs_dres else None
         return (dx, dres, outs[1], outs[2], None, None, None, None, None,
-                None, None)
+                None, None, None)
 
 
 def batch_norm_act(x, gamma, beta, running_mean, running_var,
                    momentum=0.1, eps=1e-5, training=True, relu=False,
-                   residual=None, fork=False):
+                   residual=None, fork=False, slab=None):
     """Fused BatchNorm(+residual add)(+ReLU).
 
     bf16 channels_last GPU tensors hit the CDNA4 kernels; everything else
@@ -217,7 +226,10 @@ def batch_norm_act(x, gamma, beta, running_mean, running_var,
     bitwise the same. A consumer that leaves its member unused costs
     nothing: one gradient runs the one-gradient kernels. On the
     reference path, and with SPARKDL_FUSED_RESGRAD=0 on the kernel path
-    too, the pair is ``(y, y)`` and autograd adds as usual."""
+    too, the pair is ``(y, y)`` and autograd adds as usual.
+
+    ``slab`` is for ``conv1x1_bn_act``: x's partial sums from the
+    kernel that wrote x (kernel path and training mode only)."""
     # The NHWC kernels stage per-channel folds in LDS sized for
     # C <= 2048 (csrc/batchnorm.hip `lds[kFoldFloats]`) and read bf16 in
     # 8-wide packs; larger or ragged channel counts take the reference
@@ -228,11 +240,12 @@ def batch_norm_act(x, gamma, beta, running_mean, running_var,
         if fork and os.environ.get("SPARKDL_FUSED_RESGRAD", "1") != "0":
             return _BNReLUFn.apply(x, residual, gamma, beta, running_mean,
                                    running_var, momentum, eps, training,
-                                   relu, True)
+                                   relu, True, slab)
         y = _BNReLUFn.apply(x, residual, gamma, beta, running_mean,
                             running_var, momentum, eps, training, relu,
-                            False)
+                            False, slab)
         return (y, y) if fork else y
+    assert slab is None, "a statistics slab needs the kernel path"
     # reference path: fp32 compute (stats/affine are fp32), cast back
     y = torch.nn.functional.batch_norm(
         x.float(), running_mean, running_var, gamma, beta,
@@ -701,6 +714,98 @@ def conv1x1_gemm(x_nhwc, weight):
     x2d = x_nhwc.reshape(-1, shape[-1]).contiguous()
     y = _Conv1x1Fn.apply(x2d, weight.contiguous())
     return y.reshape(*shape[:-1], weight.shape[0])
+
+
+# ---------------------------------------------------------------------------
+# 1x1 convolution forward that also writes the BatchNorm partial sums
+# ---------------------------------------------------------------------------
+
+# (Cin, Cout) of the stride-1 1x1 sites that take the fused forward by
+# default: those where scripts/probe_conv1x1_bn.py measured
+# conv1x1_stats + finalize faster than MIOpen + bn_stats_k + finalize
+# at batch 512 (profiles/probe_conv1x1_bn.log): all six stride-1 shapes
+# with Cin <= 256 of ResNet-50, by 16 to 123 us per call.
+CONV1X1_STATS_SITES = frozenset({
+    (64, 64), (64, 256), (256, 64), (256, 128), (128, 512), (256, 1024),
+})
+
+
+def conv1x1_stats_supported(cin, cout):
+    """Shapes the conv1x1_stats kernel takes at all."""
+    return cin in (64, 128, 256) and cout >= 64 and cout % 64 == 0
+
+
+def conv1x1_stats_route(cin, cout, stride=1, mode=None):
+    """Whether a 1x1 convolution followed by a training-mode BatchNorm
+    runs the fused forward. ``mode`` defaults to SPARKDL_CONV1X1_STATS:
+    "0" never, "all" wherever the kernel supports the shape, anything
+    else (the default) at CONV1X1_STATS_SITES; never under
+    SPARKDL_CONV1X1=all. The row count plays no
+    part: the kernel is exact at any M >= 1."""
+    if mode is None:
+        mode = os.environ.get("SPARKDL_CONV1X1_STATS", "1")
+    if mode == "0" or stride != 1 or not conv1x1_stats_supported(cin, cout):
+        return False
+    # SPARKDL_CONV1X1=all keeps its meaning: every 1x1 on gemm_stream
+    if os.environ.get("SPARKDL_CONV1X1", "0") == "all":
+        return False
+    return mode == "all" or (cin, cout) in CONV1X1_STATS_SITES
+
+
+class _Conv1x1StatsFn(torch.autograd.Function):
+    """y = conv1x1(x, w) on channels_last bf16 tensors through
+    conv1x1_stats: returns (y, slab), the slab (partial sums of y for
+    the BatchNorm that follows) non-differentiable. No copies:
+    channels_last [N,C,H,W] is [N*H*W, C] as a view, and so is y.
+    Backward is ATen's convolution_backward on the channels_last
+    tensors, i.e. the MIOpen dgrad and wgrad of the unfused path."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        C = _ops.ext()
+        n, cin, h, w = x.shape
+        x2d = x.permute(0, 2, 3, 1).reshape(n * h * w, cin)
+        y2d, slab = C.conv1x1_stats(x2d, weight, 0)
+        ctx.save_for_backward(x, weight)
+        ctx.mark_non_differentiable(slab)
+        # no zero tensor for the slab's absent gradient
+        ctx.set_materialize_grads(False)
+        y = y2d.view(n, h, w, weight.shape[0]).permute(0, 3, 1, 2)
+        return y, slab
+
+    @staticmethod
+    def backward(ctx, dy, _dslab):
+        if dy is None:
+            return None, None
+        x, weight = ctx.saved_tensors
+        w4 = weight.view(weight.shape[0], weight.shape[1], 1, 1)
+        dx, dw, _ = torch.ops.aten.convolution_backward(
+            dy, x, w4, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+            [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False])
+        if dw is not None:
+            dw = dw.view_as(weight)
+        return dx, dw
+
+
+def conv1x1_bn_act(x, conv, bn, residual=None, fork=False):
+    """``bn(conv(x), residual, fork)`` for a ``Conv1x1`` and a
+    ``BatchNormAct2d``, which stay the owners of the parameters and
+    buffers. Where ``conv1x1_stats_route`` says so (training mode, bf16
+    channels_last on the GPU) the convolution forward is the read-once
+    kernel that also writes the BatchNorm partial sums, and the
+    BatchNorm skips its statistics pass; otherwise, eval mode included,
+    this is exactly the two module calls."""
+    if (bn.training and x.is_cuda and x.dtype == torch.bfloat16
+            and x.dim() == 4
+            and x.is_contiguous(memory_format=torch.channels_last)
+            and bn.num_features == conv.cout
+            and conv1x1_stats_route(conv.cin, conv.cout, conv.stride)):
+        y, slab = _Conv1x1StatsFn.apply(x, conv.weight.to(x.dtype))
+        return batch_norm_act(
+            y, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+            momentum=bn.momentum, eps=bn.eps, training=True, relu=bn.relu,
+            residual=residual, fork=fork, slab=slab)
+    return bn(conv(x), residual=residual, fork=fork)
 
 
 class _LinearFusedFn(torch.autograd.Function):

@@ -158,13 +158,30 @@ class Linear(nn.Module):
 
 
 class Conv1x1(nn.Module):
-    """1x1 convolution as a row-major MFMA GEMM over NHWC rows
-    (SURVEY.md §2.2 N5 — the ResNet bottleneck reduce/expand convs).
+    """1x1 convolution over bf16 channels_last activations (SURVEY.md
+    §2.2 N5, the ResNet bottleneck reduce/expand convolutions). Owner of
+    the ``[cout, cin]`` weight; two ways in:
 
-    For stride-1 bf16 channels_last inputs with Cin % 64 == 0 the op is
-    exactly ``y[nhw, co] = x[nhw, :] @ W[co, :]^T`` on the in-house
-    256x256 16-wave GEMM kernel (dgrad included); anything else falls
-    back to the library conv. SPARKDL_CONV1X1=0 forces the fallback.
+    - Called on its own (``forward``) the default is MIOpen under the
+      committed tuning. The in-house GEMM package (gemm_stream forward
+      and dgrad, library wgrad) wins the forward at the K >= 512 sites
+      but trails MIOpen end to end (same box: MIOpen 8701 img/s,
+      K >= 512 gated 8451, all in-house 7988;
+      profiles/conv1x1_sites.log), so it stays opt-in:
+      ``SPARKDL_CONV1X1=1`` routes the K >= 512 sites in-house, ``all``
+      every stride-1 1x1 with Cin % 64 == 0.
+    - Followed by a training-mode ``BatchNormAct2d``
+      (``functional.conv1x1_bn_act``, which ResNet-50's bottlenecks
+      call) the forward alone moves to ``conv1x1_stats`` at the
+      stride-1 sites with Cin <= 256 listed in
+      ``functional.CONV1X1_STATS_SITES``: that kernel reads the input
+      once and writes the BatchNorm partial sums in its epilogue, so the
+      statistics pass over the output disappears, while dgrad and wgrad
+      stay on MIOpen. The list is the set of sites where
+      scripts/probe_conv1x1_bn.py measured the fused route faster
+      (profiles/probe_conv1x1_bn.log; profiles/README.md, "Round 7").
+      ``SPARKDL_CONV1X1_STATS=0`` restores the unfused route exactly,
+      ``all`` takes every supported shape.
     """
 
     def __init__(self, cin, cout, stride=1):
@@ -178,12 +195,7 @@ class Conv1x1(nn.Module):
     def forward(self, x):
         import os
         mode = os.environ.get("SPARKDL_CONV1X1", "0")
-        # Per-site A/B vs MIOpen (profiles/conv1x1_sites.log): the
-        # in-house GEMM forward wins at the K>=512 sites but the full
-        # fwd+dgrad+wgrad package still trails MIOpen's tuned igemm
-        # end-to-end (same-box: miopen 8701 img/s, K>=512-gated 8451,
-        # all-in-house 7988), so the DEFAULT stays on MIOpen. "1"
-        # routes the K>=512 sites in-house, "all" routes every 1x1.
+        # routing and its evidence: class docstring
         use = (self.stride == 1 and x.is_cuda
                and x.dtype == torch.bfloat16 and self.cin % 64 == 0
                and mode != "0"
