@@ -41,29 +41,32 @@
 //   bwd: reduce (1 pass) -> finalize -> apply (1 pass)
 // vs MIOpen's separate BN fwd/bwd + ReLU fwd/bwd + add kernels.
 //
-// Two-gradient backward (bn_bwd2_reduce_k, bn_bwd2_apply_k): where the
-// output has two consumers (a bottleneck's bn3 output feeds the next
-// block's conv1 and its residual branch), autograd would first add the
-// two incoming gradients in a pass of its own (3 tensors of traffic).
-// The reduce kernel takes both parts instead, forms
-// s = mask ? bf16(u + v) : 0 with ATen's rounding, writes s and
-// accumulates over it; the apply kernel reads x and s only. s is also
-// the gradient of the residual input, so the chain moves 7 tensors
-// where add + reduce + apply (with its dres store) moved 9. Geometry,
-// fold and per-element expressions are those of the one-gradient
-// kernels: dx, dres, dgamma and dbeta are bitwise the same.
-//
-// ResNet stem: BN + ReLU + MaxPool2d(3, stride 2, pad 1) as one chain
-// (bn_apply_pool_k, bn_pool_bwd_reduce_k, bn_pool_bwd_apply_k). The
-// full-resolution y, the pool's int64 indices and the full-resolution
-// dy are never written: the forward writes the pooled bf16 and one
-// byte per pooled element (the winning tap kh*3+kw, or kPoolDead where
-// the ReLU passes no gradient), and the backward kernels gather each
-// input pixel's dy from the 1, 2 or 4 windows that contain it. The
-// statistics kernels, the reduce geometry and the per-element
-// expressions (bn_affine, bn_xhat, bn_dx) are the ones of the unfused
-// chain, and the gather adds in ATen's order, so every result is
-// bitwise what bn_apply_k -> ATen max-pool (and back) gives.
+// The backward is one reduce and one apply kernel, templated on where
+// the masked gradient dym of a pixel comes from (a gradient source:
+// load() issues the global loads of one row, eval() turns them into
+// dym). Geometry, unroll, fold, slab and the per-element expressions
+// (bn_xhat, bn_dx) are the kernels', so every source gives bitwise the
+// dx, dgamma and dbeta of the unfused chain it stands for:
+//   DySrc<RELU>: dy loaded and, with RELU, masked.
+//   SumSrc<RELU>: the output has two consumers (a bottleneck's bn3
+//     output feeds the next block's conv1 and its residual branch), and
+//     autograd would first add the two incoming gradients in a pass of
+//     its own (3 tensors of traffic). The reduce kernel takes both
+//     parts instead, forms s = mask ? bf16(u + v) : 0 with ATen's
+//     rounding, writes s and accumulates over it; the apply kernel
+//     runs on DySrc<false> over s, reading x and s only. s is also the
+//     gradient of the residual input, so the chain moves 7 tensors
+//     where add + reduce + apply (with its dres store) moved 9.
+//   PoolSrc: the ResNet stem, BN + ReLU + MaxPool2d(3, stride 2, pad 1)
+//     as one chain with bn_apply_pool_k. The full-resolution y, the
+//     pool's int64 indices and the full-resolution dy are never
+//     written: the forward writes the pooled bf16 and one byte per
+//     pooled element (the winning tap kh*3+kw, or kPoolDead where the
+//     ReLU passes no gradient), and the source gathers each input
+//     pixel's dy from the 1, 2 or 4 windows that contain it. The
+//     forward rounds with bn_affine as bn_apply_k does and the gather
+//     adds in ATen's order, so every result is bitwise what
+//     bn_apply_k -> ATen max-pool (and back) gives.
 
 #include "common.hip.h"
 #include "kernels.h"
@@ -81,6 +84,34 @@ constexpr int kFoldFloats = kBlock * 2 * kVec;  // 16 KB
 // Second stage: each block finalizes kFinCh channels with
 // kBlock / kFinCh = 64 slab-row lanes per channel.
 constexpr int kFinCh = 4;
+
+// Rows that one block pass covers: cols / kVec threads hold a row
+// (cols % 8 == 0), and past 256 of them a row takes the whole block.
+__host__ __device__ inline int bn_rows_per_block(int cols) {
+  return kBlock / min(cols / kVec, kBlock);
+}
+
+// A thread's place in that pass: its row (row_off < rpb, else idle) and
+// the first of its kVec columns.
+struct BnGeom {
+  int rpb, lane_col, row_off;
+};
+__device__ __forceinline__ BnGeom bn_geom(int cols) {
+  const int tpr = cols / kVec;
+  return {bn_rows_per_block(cols), (int)((threadIdx.x % tpr) * kVec),
+          (int)(threadIdx.x / tpr)};
+}
+
+// The kVec per-channel floats of a lane, from p = base + lane_col.
+struct Chan8 {
+  float4v lo, hi;
+  __device__ __forceinline__ float operator[](int j) const {
+    return j < 4 ? lo[j] : hi[j - 4];
+  }
+};
+__device__ __forceinline__ Chan8 bn_chan8(const float* __restrict__ p) {
+  return {*(const float4v*)(p), *(const float4v*)(p + 4)};
+}
 
 // Per-element expressions, shared by the plain and the pooled kernels
 // so that both contract and round alike.
@@ -207,21 +238,18 @@ __global__ __launch_bounds__(kBlock) void bn_stats_k(
     const short* __restrict__ x, float* __restrict__ slab,
     long long rows, int cols) {
   __shared__ __attribute__((aligned(16))) float lds[kFoldFloats];
-  const int tpr = cols / kVec;             // threads per row (cols%8==0)
-  const int rpb = kBlock / min(tpr, kBlock);
-  const int lane_col = (threadIdx.x % tpr) * kVec;
-  const int row_off = threadIdx.x / tpr;
+  const BnGeom t = bn_geom(cols);
 
   float s[kVec] = {0.f}, ss[kVec] = {0.f};
-  if (row_off < rpb) {
-    const long long stride = (long long)gridDim.x * rpb;
-    long long r = (long long)blockIdx.x * rpb + row_off;
+  if (t.row_off < t.rpb) {
+    const long long stride = (long long)gridDim.x * t.rpb;
+    long long r = (long long)blockIdx.x * t.rpb + t.row_off;
     // U rows of loads issued before the first use
     for (; r + (U - 1) * stride < rows; r += U * stride) {
       short8 v[U];
 #pragma unroll
       for (int u = 0; u < U; ++u)
-        v[u] = *(const short8*)(x + (r + u * stride) * cols + lane_col);
+        v[u] = *(const short8*)(x + (r + u * stride) * cols + t.lane_col);
 #pragma unroll
       for (int u = 0; u < U; ++u) {
 #pragma unroll
@@ -233,7 +261,7 @@ __global__ __launch_bounds__(kBlock) void bn_stats_k(
       }
     }
     for (; r < rows; r += stride) {
-      const short8 v = *(const short8*)(x + r * cols + lane_col);
+      const short8 v = *(const short8*)(x + r * cols + t.lane_col);
 #pragma unroll
       for (int j = 0; j < kVec; ++j) {
         const float f = bf2f(v[j]);
@@ -242,7 +270,7 @@ __global__ __launch_bounds__(kBlock) void bn_stats_k(
       }
     }
   }
-  bn_block_fold(lds, s, ss, rpb, row_off, lane_col, cols,
+  bn_block_fold(lds, s, ss, t.rpb, t.row_off, t.lane_col, cols,
                 slab + (size_t)blockIdx.x * 2 * cols);
 }
 
@@ -293,26 +321,20 @@ __global__ __launch_bounds__(kBlock) void bn_apply_k(
     const float* __restrict__ scale, const float* __restrict__ shift,
     short* __restrict__ y, unsigned char* __restrict__ mask,
     long long rows, int cols) {
-  const int tpr = cols / kVec;
-  const int rpb = kBlock / min(tpr, kBlock);
-  const int lane_col = (threadIdx.x % tpr) * kVec;
-  const int row_off = threadIdx.x / tpr;
-  if (row_off >= rpb) return;
-  const float4v sc0 = *(const float4v*)(scale + lane_col);
-  const float4v sc1 = *(const float4v*)(scale + lane_col + 4);
-  const float4v sh0 = *(const float4v*)(shift + lane_col);
-  const float4v sh1 = *(const float4v*)(shift + lane_col + 4);
+  const BnGeom t = bn_geom(cols);
+  if (t.row_off >= t.rpb) return;
+  const Chan8 sc = bn_chan8(scale + t.lane_col);
+  const Chan8 sh = bn_chan8(shift + t.lane_col);
 
-  for (long long r = (long long)blockIdx.x * rpb + row_off; r < rows;
-       r += (long long)gridDim.x * rpb) {
-    const long long base = r * cols + lane_col;
+  for (long long r = (long long)blockIdx.x * t.rpb + t.row_off; r < rows;
+       r += (long long)gridDim.x * t.rpb) {
+    const long long base = r * cols + t.lane_col;
     const short8 v = *(const short8*)(x + base);
     short8 o;
     unsigned char mbits = 0;
 #pragma unroll
     for (int j = 0; j < kVec; ++j) {
-      float f = bn_affine(v[j], j < 4 ? sc0[j] : sc1[j - 4],
-                          j < 4 ? sh0[j] : sh1[j - 4]);
+      float f = bn_affine(v[j], sc[j], sh[j]);
       if (RES) f += bf2f(res[base + j]);
       if (RELU) {
         if (f > 0.f) mbits |= (unsigned char)(1u << j);
@@ -321,74 +343,166 @@ __global__ __launch_bounds__(kBlock) void bn_apply_k(
       o[j] = f2bf(f);
     }
     *(short8*)(y + base) = o;
-    if (RELU) mask[(r * cols + lane_col) / kVec] = mbits;
+    if (RELU) mask[(r * cols + t.lane_col) / kVec] = mbits;
   }
 }
 
 // --------------------------------------------------------------------
 // Backward
 // --------------------------------------------------------------------
-// dym = dy * relu_mask (mask from saved output y > 0).
-// slab row layout: [0..C) sum(dym), [C..2C) sum(dym * xhat)
+// Image and pooled sizes of the stem chain (PoolSrc).
+struct PoolGeom {
+  int H, W, Ho, Wo;
+};
 
-template <bool RELU, int U>
+// A gradient source gives dym = dy * relu_mask (mask from the saved
+// output y > 0) of the kVec elements at offset base = r*cols + lane_col:
+//   Row load(base, r, cols, lane_col): every global load the row needs
+//     and no arithmetic on what they return, so that the reduce kernel
+//     can issue U rows of loads before the first use. base comes from
+//     the kernel, which addresses x with it; a source that forms it
+//     again costs the apply kernels registers and occupancy;
+//   float eval(row, j): dym of element j from the loaded values, one
+//     element at a time inside the kernels' own loop over j. With a
+//     row's gradients formed ahead of that loop the compiler no longer
+//     folds dres = bf16(dym) of an unmasked dy to dy;
+//   make(bytes, ga, gb, s, g): the source over the kernels' operands: a
+//     byte plane of the forward, up to two gradients, a row to write
+//     back, the pool geometry. They are kernel parameters of their own
+//     because only those carry __restrict__ (on struct members it is
+//     ignored): with the pointers inside a struct argument the masked
+//     reduce kernel no longer issues its loads ahead of the first use;
+//   kStores: the source also writes the row back (store(row, base)),
+//     which only the reduce kernel does.
+// The measurements behind the choices in load, eval and make are in
+// profiles/bn_refactor_isa.txt.
+
+// dy * mask; without RELU the mask is neither loaded nor applied.
+template <bool RELU>
+struct DySrc {
+  static constexpr bool kStores = false;
+  const unsigned char* mask;
+  const short* dy;
+  static __device__ __forceinline__ DySrc make(
+      const unsigned char* mask, const short* dy, const short*, short*,
+      const PoolGeom&) {
+    return {mask, dy};
+  }
+  struct Row {
+    short8 dy;
+    unsigned char mbits;
+  };
+  __device__ __forceinline__ Row load(long long base, long long, int,
+                                      int) const {
+    Row t;
+    t.dy = *(const short8*)(dy + base);
+    t.mbits = 0xffu;
+    if (RELU) t.mbits = mask[base / kVec];
+    return t;
+  }
+  __device__ __forceinline__ float eval(const Row& t, int j) const {
+    float d = bf2f(t.dy[j]);
+    if (RELU && !(t.mbits & (1u << j))) d = 0.f;
+    return d;
+  }
+};
+
+// The output fed two consumers and dy = u + v arrives as its two parts.
+// s = mask ? bf16(u + v) : 0 is the dy * mask of DySrc and, rounded as
+// ATen rounds its bf16 add, also its dres. Only the reduce kernel runs
+// on this source: it stores s, the apply kernel then reads it back as
+// DySrc<false> in place of dy and the mask, and the caller hands it on
+// as the residual gradient.
+template <bool RELU>
+struct SumSrc {
+  static constexpr bool kStores = true;
+  const unsigned char* mask;
+  const short* dya;
+  const short* dyb;
+  short* s;
+  static __device__ __forceinline__ SumSrc make(
+      const unsigned char* mask, const short* dya, const short* dyb,
+      short* s, const PoolGeom&) {
+    return {mask, dya, dyb, s};
+  }
+  struct Row {
+    short8 ua, ub, sv;  // sv: s of the row, filled by eval
+    unsigned char mbits;
+  };
+  __device__ __forceinline__ Row load(long long base, long long, int,
+                                      int) const {
+    Row t;
+    t.ua = *(const short8*)(dya + base);
+    t.ub = *(const short8*)(dyb + base);
+    t.mbits = 0xffu;
+    if (RELU) t.mbits = mask[base / kVec];
+    return t;
+  }
+  __device__ __forceinline__ float eval(Row& t, int j) const {
+    short sb = f2bf(bf2f(t.ua[j]) + bf2f(t.ub[j]));
+    if (RELU && !(t.mbits & (1u << j))) sb = 0;
+    t.sv[j] = sb;
+    return bf2f(sb);
+  }
+  __device__ __forceinline__ void store(const Row& t,
+                                        long long base) const {
+    *(short8*)(s + base) = t.sv;
+  }
+};
+
+// slab row layout: [0..C) sum(dym), [C..2C) sum(dym * xhat)
+template <class Src, int U>
 __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_k(
-    const short* __restrict__ x, const unsigned char* __restrict__ mask,
-    const short* __restrict__ dy, const float* __restrict__ save_mean,
+    const short* __restrict__ x, const unsigned char* __restrict__ bytes,
+    const short* __restrict__ ga, const short* __restrict__ gb,
+    short* __restrict__ s, PoolGeom g,
+    const float* __restrict__ save_mean,
     const float* __restrict__ save_rstd, float* __restrict__ slab,
     long long rows, int cols) {
   __shared__ __attribute__((aligned(16))) float lds[kFoldFloats];
-  const int tpr = cols / kVec;
-  const int rpb = kBlock / min(tpr, kBlock);
-  const int lane_col = (threadIdx.x % tpr) * kVec;
-  const int row_off = threadIdx.x / tpr;
+  const Src src = Src::make(bytes, ga, gb, s, g);
+  const BnGeom t = bn_geom(cols);
 
   float s1[kVec] = {0.f}, s2[kVec] = {0.f};
-  if (row_off < rpb) {
-    const float4v m0 = *(const float4v*)(save_mean + lane_col);
-    const float4v m1 = *(const float4v*)(save_mean + lane_col + 4);
-    const float4v r0 = *(const float4v*)(save_rstd + lane_col);
-    const float4v r1 = *(const float4v*)(save_rstd + lane_col + 4);
-    auto accum = [&](const short8& xv, const short8& dv,
-                     unsigned char mbits) {
+  if (t.row_off < t.rpb) {
+    const Chan8 mean = bn_chan8(save_mean + t.lane_col);
+    const Chan8 rstd = bn_chan8(save_rstd + t.lane_col);
+    auto accum = [&](const short8& xv, typename Src::Row& row,
+                     long long base) {
 #pragma unroll
       for (int j = 0; j < kVec; ++j) {
-        float d = bf2f(dv[j]);
-        if (RELU && !(mbits & (1u << j))) d = 0.f;
-        const float mean = j < 4 ? m0[j] : m1[j - 4];
-        const float rstd = j < 4 ? r0[j] : r1[j - 4];
-        const float xh = bn_xhat(xv[j], mean, rstd);
+        const float d = src.eval(row, j);
+        const float xh = bn_xhat(xv[j], mean[j], rstd[j]);
         s1[j] += d;
         s2[j] += d * xh;
       }
+      if constexpr (Src::kStores) src.store(row, base);
     };
-    const long long stride = (long long)gridDim.x * rpb;
-    long long r = (long long)blockIdx.x * rpb + row_off;
+    const long long stride = (long long)gridDim.x * t.rpb;
+    long long r = (long long)blockIdx.x * t.rpb + t.row_off;
     // U rows of loads issued before the first use
     for (; r + (U - 1) * stride < rows; r += U * stride) {
-      short8 xv[U], dv[U];
-      unsigned char mb[U];
+      short8 xv[U];
+      typename Src::Row row[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const long long base = (r + u * stride) * cols + lane_col;
+        const long long ru = r + u * stride;
+        const long long base = ru * cols + t.lane_col;
         xv[u] = *(const short8*)(x + base);
-        dv[u] = *(const short8*)(dy + base);
-        mb[u] = 0xffu;
-        if (RELU) mb[u] = mask[base / kVec];
+        row[u] = src.load(base, ru, cols, t.lane_col);
       }
 #pragma unroll
-      for (int u = 0; u < U; ++u) accum(xv[u], dv[u], mb[u]);
+      for (int u = 0; u < U; ++u)
+        accum(xv[u], row[u], (r + u * stride) * cols + t.lane_col);
     }
     for (; r < rows; r += stride) {
-      const long long base = r * cols + lane_col;
+      const long long base = r * cols + t.lane_col;
       const short8 xv = *(const short8*)(x + base);
-      const short8 dv = *(const short8*)(dy + base);
-      unsigned char mbits = 0xffu;
-      if (RELU) mbits = mask[base / kVec];
-      accum(xv, dv, mbits);
+      typename Src::Row row = src.load(base, r, cols, t.lane_col);
+      accum(xv, row, base);
     }
   }
-  bn_block_fold(lds, s1, s2, rpb, row_off, lane_col, cols,
+  bn_block_fold(lds, s1, s2, t.rpb, t.row_off, t.lane_col, cols,
                 slab + (size_t)blockIdx.x * 2 * cols);
 }
 
@@ -419,178 +533,41 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_finalize_k(
 }
 
 // dx = c1*(dym - c2 - xhat*c3); optional dres = dym.
-template <bool RELU, bool RES>
+template <class Src, bool RES>
 __global__ __launch_bounds__(kBlock) void bn_bwd_apply_k(
-    const short* __restrict__ x, const unsigned char* __restrict__ mask,
-    const short* __restrict__ dy, const float* __restrict__ save_mean,
+    const short* __restrict__ x, const unsigned char* __restrict__ bytes,
+    const short* __restrict__ ga, const short* __restrict__ gb,
+    short* __restrict__ s, PoolGeom g,
+    const float* __restrict__ save_mean,
     const float* __restrict__ save_rstd, const float* __restrict__ c1,
     const float* __restrict__ c2, const float* __restrict__ c3,
     short* __restrict__ dx, short* __restrict__ dres, long long rows,
     int cols) {
-  const int tpr = cols / kVec;
-  const int rpb = kBlock / min(tpr, kBlock);
-  const int lane_col = (threadIdx.x % tpr) * kVec;
-  const int row_off = threadIdx.x / tpr;
-  if (row_off >= rpb) return;
-  const float4v m0 = *(const float4v*)(save_mean + lane_col);
-  const float4v m1 = *(const float4v*)(save_mean + lane_col + 4);
-  const float4v r0 = *(const float4v*)(save_rstd + lane_col);
-  const float4v r1 = *(const float4v*)(save_rstd + lane_col + 4);
-  const float4v a0 = *(const float4v*)(c1 + lane_col);
-  const float4v a1 = *(const float4v*)(c1 + lane_col + 4);
-  const float4v b0 = *(const float4v*)(c2 + lane_col);
-  const float4v b1 = *(const float4v*)(c2 + lane_col + 4);
-  const float4v g0 = *(const float4v*)(c3 + lane_col);
-  const float4v g1 = *(const float4v*)(c3 + lane_col + 4);
+  static_assert(!Src::kStores, "only the reduce kernel writes a row back");
+  const Src src = Src::make(bytes, ga, gb, s, g);
+  const BnGeom t = bn_geom(cols);
+  if (t.row_off >= t.rpb) return;
+  const Chan8 mean = bn_chan8(save_mean + t.lane_col);
+  const Chan8 rstd = bn_chan8(save_rstd + t.lane_col);
+  const Chan8 k1 = bn_chan8(c1 + t.lane_col);
+  const Chan8 k2 = bn_chan8(c2 + t.lane_col);
+  const Chan8 k3 = bn_chan8(c3 + t.lane_col);
 
-  for (long long r = (long long)blockIdx.x * rpb + row_off; r < rows;
-       r += (long long)gridDim.x * rpb) {
-    const long long base = r * cols + lane_col;
+  for (long long r = (long long)blockIdx.x * t.rpb + t.row_off; r < rows;
+       r += (long long)gridDim.x * t.rpb) {
+    const long long base = r * cols + t.lane_col;
     const short8 xv = *(const short8*)(x + base);
-    const short8 dv = *(const short8*)(dy + base);
-    unsigned char mbits = 0xffu;
-    if (RELU) mbits = mask[base / kVec];
+    typename Src::Row row = src.load(base, r, cols, t.lane_col);
     short8 odx, odr;
 #pragma unroll
     for (int j = 0; j < kVec; ++j) {
-      float d = bf2f(dv[j]);
-      if (RELU && !(mbits & (1u << j))) d = 0.f;
-      const float mean = j < 4 ? m0[j] : m1[j - 4];
-      const float rstd = j < 4 ? r0[j] : r1[j - 4];
-      const float xh = bn_xhat(xv[j], mean, rstd);
-      const float k1 = j < 4 ? a0[j] : a1[j - 4];
-      const float k2 = j < 4 ? b0[j] : b1[j - 4];
-      const float k3 = j < 4 ? g0[j] : g1[j - 4];
-      odx[j] = f2bf(bn_dx(d, xh, k1, k2, k3));
+      const float d = src.eval(row, j);
+      const float xh = bn_xhat(xv[j], mean[j], rstd[j]);
+      odx[j] = f2bf(bn_dx(d, xh, k1[j], k2[j], k3[j]));
       if (RES) odr[j] = f2bf(d);
     }
     *(short8*)(dx + base) = odx;
     if (RES) *(short8*)(dres + base) = odr;
-  }
-}
-
-// --------------------------------------------------------------------
-// Backward with two incoming gradients
-// --------------------------------------------------------------------
-// The output feeds two consumers and dy = u + v arrives as its two
-// parts. s = mask ? bf16(u + v) : 0 is the dy * mask of the chain above
-// and, rounded as ATen rounds its bf16 add, also its dres: the reduce
-// kernel writes it once, the apply kernel reads it back in place of dy
-// and the mask, and the caller hands it on as the residual gradient.
-
-// bn_bwd_reduce_k<RELU, U> over d = s: same grid, rows per block,
-// unroll, fold and slab.
-template <bool RELU, int U>
-__global__ __launch_bounds__(kBlock) void bn_bwd2_reduce_k(
-    const short* __restrict__ x, const unsigned char* __restrict__ mask,
-    const short* __restrict__ dya, const short* __restrict__ dyb,
-    const float* __restrict__ save_mean,
-    const float* __restrict__ save_rstd, short* __restrict__ s,
-    float* __restrict__ slab, long long rows, int cols) {
-  __shared__ __attribute__((aligned(16))) float lds[kFoldFloats];
-  const int tpr = cols / kVec;
-  const int rpb = kBlock / min(tpr, kBlock);
-  const int lane_col = (threadIdx.x % tpr) * kVec;
-  const int row_off = threadIdx.x / tpr;
-
-  float s1[kVec] = {0.f}, s2[kVec] = {0.f};
-  if (row_off < rpb) {
-    const float4v m0 = *(const float4v*)(save_mean + lane_col);
-    const float4v m1 = *(const float4v*)(save_mean + lane_col + 4);
-    const float4v r0 = *(const float4v*)(save_rstd + lane_col);
-    const float4v r1 = *(const float4v*)(save_rstd + lane_col + 4);
-    auto accum = [&](const short8& xv, const short8& ua, const short8& ub,
-                     unsigned char mbits, long long base) {
-      short8 sv;
-#pragma unroll
-      for (int j = 0; j < kVec; ++j) {
-        short sb = f2bf(bf2f(ua[j]) + bf2f(ub[j]));
-        if (RELU && !(mbits & (1u << j))) sb = 0;
-        sv[j] = sb;
-        const float d = bf2f(sb);
-        const float mean = j < 4 ? m0[j] : m1[j - 4];
-        const float rstd = j < 4 ? r0[j] : r1[j - 4];
-        const float xh = bn_xhat(xv[j], mean, rstd);
-        s1[j] += d;
-        s2[j] += d * xh;
-      }
-      *(short8*)(s + base) = sv;
-    };
-    const long long stride = (long long)gridDim.x * rpb;
-    long long r = (long long)blockIdx.x * rpb + row_off;
-    // U rows of loads issued before the first use
-    for (; r + (U - 1) * stride < rows; r += U * stride) {
-      short8 xv[U], ua[U], ub[U];
-      unsigned char mb[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const long long base = (r + u * stride) * cols + lane_col;
-        xv[u] = *(const short8*)(x + base);
-        ua[u] = *(const short8*)(dya + base);
-        ub[u] = *(const short8*)(dyb + base);
-        mb[u] = 0xffu;
-        if (RELU) mb[u] = mask[base / kVec];
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        accum(xv[u], ua[u], ub[u], mb[u],
-              (r + u * stride) * cols + lane_col);
-    }
-    for (; r < rows; r += stride) {
-      const long long base = r * cols + lane_col;
-      const short8 xv = *(const short8*)(x + base);
-      const short8 ua = *(const short8*)(dya + base);
-      const short8 ub = *(const short8*)(dyb + base);
-      unsigned char mbits = 0xffu;
-      if (RELU) mbits = mask[base / kVec];
-      accum(xv, ua, ub, mbits, base);
-    }
-  }
-  bn_block_fold(lds, s1, s2, rpb, row_off, lane_col, cols,
-                slab + (size_t)blockIdx.x * 2 * cols);
-}
-
-// dx = c1*(s - c2 - xhat*c3): bn_bwd_apply_k on the masked sum, with no
-// mask to load and no dres to store.
-__global__ __launch_bounds__(kBlock) void bn_bwd2_apply_k(
-    const short* __restrict__ x, const short* __restrict__ s,
-    const float* __restrict__ save_mean,
-    const float* __restrict__ save_rstd, const float* __restrict__ c1,
-    const float* __restrict__ c2, const float* __restrict__ c3,
-    short* __restrict__ dx, long long rows, int cols) {
-  const int tpr = cols / kVec;
-  const int rpb = kBlock / min(tpr, kBlock);
-  const int lane_col = (threadIdx.x % tpr) * kVec;
-  const int row_off = threadIdx.x / tpr;
-  if (row_off >= rpb) return;
-  const float4v m0 = *(const float4v*)(save_mean + lane_col);
-  const float4v m1 = *(const float4v*)(save_mean + lane_col + 4);
-  const float4v r0 = *(const float4v*)(save_rstd + lane_col);
-  const float4v r1 = *(const float4v*)(save_rstd + lane_col + 4);
-  const float4v a0 = *(const float4v*)(c1 + lane_col);
-  const float4v a1 = *(const float4v*)(c1 + lane_col + 4);
-  const float4v b0 = *(const float4v*)(c2 + lane_col);
-  const float4v b1 = *(const float4v*)(c2 + lane_col + 4);
-  const float4v g0 = *(const float4v*)(c3 + lane_col);
-  const float4v g1 = *(const float4v*)(c3 + lane_col + 4);
-
-  for (long long r = (long long)blockIdx.x * rpb + row_off; r < rows;
-       r += (long long)gridDim.x * rpb) {
-    const long long base = r * cols + lane_col;
-    const short8 xv = *(const short8*)(x + base);
-    const short8 sv = *(const short8*)(s + base);
-    short8 odx;
-#pragma unroll
-    for (int j = 0; j < kVec; ++j) {
-      const float mean = j < 4 ? m0[j] : m1[j - 4];
-      const float rstd = j < 4 ? r0[j] : r1[j - 4];
-      const float xh = bn_xhat(xv[j], mean, rstd);
-      const float k1 = j < 4 ? a0[j] : a1[j - 4];
-      const float k2 = j < 4 ? b0[j] : b1[j - 4];
-      const float k3 = j < 4 ? g0[j] : g1[j - 4];
-      odx[j] = f2bf(bn_dx(bf2f(sv[j]), xh, k1, k2, k3));
-    }
-    *(short8*)(dx + base) = odx;
   }
 }
 
@@ -607,10 +584,6 @@ typedef unsigned uint2v __attribute__((ext_vector_type(2)));
 constexpr unsigned kPoolDead = 9;
 // Never stored: what a window that does not exist is compared against.
 constexpr unsigned kPoolNone = 0xffu;
-
-struct PoolGeom {
-  int H, W, Ho, Wo;
-};
 
 // pooled = maxpool(relu(scale*x + shift)), one thread per output pixel
 // and 8 channels. Every tap is computed and rounded to bf16 as
@@ -630,19 +603,14 @@ __global__ __launch_bounds__(kBlock) void bn_apply_pool_k(
     const float* __restrict__ shift, short* __restrict__ pooled,
     unsigned char* __restrict__ code, long long orows, int cols,
     PoolGeom g) {
-  const int tpr = cols / kVec;
-  const int rpb = kBlock / min(tpr, kBlock);
-  const int lane_col = (threadIdx.x % tpr) * kVec;
-  const int row_off = threadIdx.x / tpr;
-  if (row_off >= rpb) return;
-  const float4v sc0 = *(const float4v*)(scale + lane_col);
-  const float4v sc1 = *(const float4v*)(scale + lane_col + 4);
-  const float4v sh0 = *(const float4v*)(shift + lane_col);
-  const float4v sh1 = *(const float4v*)(shift + lane_col + 4);
+  const BnGeom t = bn_geom(cols);
+  if (t.row_off >= t.rpb) return;
+  const Chan8 sc = bn_chan8(scale + t.lane_col);
+  const Chan8 sh = bn_chan8(shift + t.lane_col);
   const unsigned opix = (unsigned)(g.Ho * g.Wo);
 
-  for (long long o = (long long)blockIdx.x * rpb + row_off; o < orows;
-       o += (long long)gridDim.x * rpb) {
+  for (long long o = (long long)blockIdx.x * t.rpb + t.row_off; o < orows;
+       o += (long long)gridDim.x * t.rpb) {
     const unsigned n = (unsigned)o / opix;
     const unsigned rem = (unsigned)o - n * opix;
     const int oh = (int)(rem / (unsigned)g.Wo);
@@ -657,7 +625,7 @@ __global__ __launch_bounds__(kBlock) void bn_apply_pool_k(
       for (int kw = 0; kw < 3; ++kw) {
         const int iw = min(max(2 * ow - 1 + kw, 0), g.W - 1);
         const long long r = ((long long)n * g.H + ih) * g.W + iw;
-        v[kh * 3 + kw] = *(const short8*)(x + r * cols + lane_col);
+        v[kh * 3 + kw] = *(const short8*)(x + r * cols + t.lane_col);
       }
     }
     float best[kVec], bestf[kVec];
@@ -678,9 +646,7 @@ __global__ __launch_bounds__(kBlock) void bn_apply_pool_k(
         const bool in = hin && iw >= 0 && iw < g.W;
 #pragma unroll
         for (int j = 0; j < kVec; ++j) {
-          const float f =
-              bn_affine(v[kh * 3 + kw][j], j < 4 ? sc0[j] : sc1[j - 4],
-                        j < 4 ? sh0[j] : sh1[j - 4]);
+          const float f = bn_affine(v[kh * 3 + kw][j], sc[j], sh[j]);
           const float q = bf2f(f2bf(fmaxf(f, 0.f)));
           // a branch, not selects: most taps replace no maximum, and
           // the branch-free form measured slower (stem forward chain
@@ -704,7 +670,7 @@ __global__ __launch_bounds__(kBlock) void bn_apply_pool_k(
       if (j < 4) c0 |= c << (8 * j);
       else c1 |= c << (8 * (j - 4));
     }
-    const long long base = o * cols + lane_col;
+    const long long base = o * cols + t.lane_col;
     *(short8*)(pooled + base) = ov;
     *(uint2v*)(code + base) = uint2v{c0, c1};
   }
@@ -757,145 +723,138 @@ __device__ __forceinline__ PoolTaps bn_pool_taps(
 // dym of the pixel: fp32 sum of the pooled gradients whose code names
 // it, rounded to bf16, which is the dy * mask that the unfused chain
 // hands to bn_bwd_reduce_k / bn_bwd_apply_k.
-__device__ __forceinline__ void bn_pool_dym(const PoolTaps& t,
-                                            float (&d)[kVec]) {
-#pragma unroll
-  for (int j = 0; j < kVec; ++j) d[j] = 0.f;
+__device__ __forceinline__ float bn_pool_dym(const PoolTaps& t, int j) {
+  float d = 0.f;
 #pragma unroll
   for (int w = 0; w < 4; ++w) {
-#pragma unroll
-    for (int j = 0; j < kVec; ++j) {
-      const unsigned c =
-          ((j < 4 ? t.code[w][0] : t.code[w][1]) >> (8 * (j & 3))) & 0xffu;
-      if (c == t.want[w]) d[j] += bf2f(t.dy[w][j]);
-    }
+    const unsigned c =
+        ((j < 4 ? t.code[w][0] : t.code[w][1]) >> (8 * (j & 3))) & 0xffu;
+    if (c == t.want[w]) d += bf2f(t.dy[w][j]);
   }
-#pragma unroll
-  for (int j = 0; j < kVec; ++j) d[j] = bf2f(f2bf(d[j]));
+  return bf2f(f2bf(d));
 }
 
-// bn_bwd_reduce_k<true, U> with dym gathered instead of loaded: same
-// grid, rows per block, unroll, fold and slab.
-template <int U>
-__global__ __launch_bounds__(kBlock) void bn_pool_bwd_reduce_k(
-    const short* __restrict__ x, const unsigned char* __restrict__ code,
-    const short* __restrict__ dyp, const float* __restrict__ save_mean,
-    const float* __restrict__ save_rstd, float* __restrict__ slab,
-    long long rows, int cols, PoolGeom g) {
-  __shared__ __attribute__((aligned(16))) float lds[kFoldFloats];
-  const int tpr = cols / kVec;
-  const int rpb = kBlock / min(tpr, kBlock);
-  const int lane_col = (threadIdx.x % tpr) * kVec;
-  const int row_off = threadIdx.x / tpr;
-
-  float s1[kVec] = {0.f}, s2[kVec] = {0.f};
-  if (row_off < rpb) {
-    const float4v m0 = *(const float4v*)(save_mean + lane_col);
-    const float4v m1 = *(const float4v*)(save_mean + lane_col + 4);
-    const float4v r0 = *(const float4v*)(save_rstd + lane_col);
-    const float4v r1 = *(const float4v*)(save_rstd + lane_col + 4);
-    auto accum = [&](const short8& xv, const PoolTaps& t) {
-      float d[kVec];
-      bn_pool_dym(t, d);
-#pragma unroll
-      for (int j = 0; j < kVec; ++j) {
-        const float mean = j < 4 ? m0[j] : m1[j - 4];
-        const float rstd = j < 4 ? r0[j] : r1[j - 4];
-        const float xh = bn_xhat(xv[j], mean, rstd);
-        s1[j] += d[j];
-        s2[j] += d[j] * xh;
-      }
-    };
-    const long long stride = (long long)gridDim.x * rpb;
-    long long r = (long long)blockIdx.x * rpb + row_off;
-    // U rows of loads issued before the first use
-    for (; r + (U - 1) * stride < rows; r += U * stride) {
-      short8 xv[U];
-      PoolTaps t[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const long long ru = r + u * stride;
-        xv[u] = *(const short8*)(x + ru * cols + lane_col);
-        t[u] = bn_pool_taps(dyp, code, ru, cols, lane_col, g);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) accum(xv[u], t[u]);
-    }
-    for (; r < rows; r += stride) {
-      const short8 xv = *(const short8*)(x + r * cols + lane_col);
-      const PoolTaps t = bn_pool_taps(dyp, code, r, cols, lane_col, g);
-      accum(xv, t);
-    }
+// dym gathered from the pooled gradient instead of loaded: the source
+// of the stem's backward (DySrc<true> of the unfused chain).
+struct PoolSrc {
+  static constexpr bool kStores = false;
+  const unsigned char* code;
+  const short* dyp;
+  PoolGeom g;
+  static __device__ __forceinline__ PoolSrc make(
+      const unsigned char* code, const short* dyp, const short*, short*,
+      const PoolGeom& g) {
+    return {code, dyp, g};
   }
-  bn_block_fold(lds, s1, s2, rpb, row_off, lane_col, cols,
-                slab + (size_t)blockIdx.x * 2 * cols);
-}
-
-// bn_bwd_apply_k<true, false> with dym gathered instead of loaded.
-__global__ __launch_bounds__(kBlock) void bn_pool_bwd_apply_k(
-    const short* __restrict__ x, const unsigned char* __restrict__ code,
-    const short* __restrict__ dyp, const float* __restrict__ save_mean,
-    const float* __restrict__ save_rstd, const float* __restrict__ c1,
-    const float* __restrict__ c2, const float* __restrict__ c3,
-    short* __restrict__ dx, long long rows, int cols, PoolGeom g) {
-  const int tpr = cols / kVec;
-  const int rpb = kBlock / min(tpr, kBlock);
-  const int lane_col = (threadIdx.x % tpr) * kVec;
-  const int row_off = threadIdx.x / tpr;
-  if (row_off >= rpb) return;
-  const float4v m0 = *(const float4v*)(save_mean + lane_col);
-  const float4v m1 = *(const float4v*)(save_mean + lane_col + 4);
-  const float4v r0 = *(const float4v*)(save_rstd + lane_col);
-  const float4v r1 = *(const float4v*)(save_rstd + lane_col + 4);
-  const float4v a0 = *(const float4v*)(c1 + lane_col);
-  const float4v a1 = *(const float4v*)(c1 + lane_col + 4);
-  const float4v b0 = *(const float4v*)(c2 + lane_col);
-  const float4v b1 = *(const float4v*)(c2 + lane_col + 4);
-  const float4v g0 = *(const float4v*)(c3 + lane_col);
-  const float4v g1 = *(const float4v*)(c3 + lane_col + 4);
-
-  for (long long r = (long long)blockIdx.x * rpb + row_off; r < rows;
-       r += (long long)gridDim.x * rpb) {
-    const long long base = r * cols + lane_col;
-    const short8 xv = *(const short8*)(x + base);
-    const PoolTaps t = bn_pool_taps(dyp, code, r, cols, lane_col, g);
-    float d[kVec];
-    bn_pool_dym(t, d);
-    short8 odx;
-#pragma unroll
-    for (int j = 0; j < kVec; ++j) {
-      const float mean = j < 4 ? m0[j] : m1[j - 4];
-      const float rstd = j < 4 ? r0[j] : r1[j - 4];
-      const float xh = bn_xhat(xv[j], mean, rstd);
-      const float k1 = j < 4 ? a0[j] : a1[j - 4];
-      const float k2 = j < 4 ? b0[j] : b1[j - 4];
-      const float k3 = j < 4 ? g0[j] : g1[j - 4];
-      odx[j] = f2bf(bn_dx(d[j], xh, k1, k2, k3));
-    }
-    *(short8*)(dx + base) = odx;
+  using Row = PoolTaps;
+  __device__ __forceinline__ Row load(long long, long long r, int cols,
+                                      int lane_col) const {
+    return bn_pool_taps(dyp, code, r, cols, lane_col, g);
   }
+  __device__ __forceinline__ float eval(const Row& t, int j) const {
+    return bn_pool_dym(t, j);
+  }
+};
+
+long long bn_row_blocks(long long rows, int cols) {
+  const int rpb = bn_rows_per_block(cols);
+  return (rows + rpb - 1) / rpb;
 }
 
 int bn_grid(long long rows, int cols) {
-  const int tpr = cols / kVec;
-  const int rpb = kBlock / min(tpr, kBlock);
-  long long blocks = (rows + rpb - 1) / rpb;
-  return (int)min(blocks, 2048LL);
+  return (int)min(bn_row_blocks(rows, cols), 2048LL);
 }
 
 }  // namespace
 
 // Reduce grid = slab rows; the rule is derived in the header comment.
 int bn_reduce_blocks(long long rows, int cols) {
-  const int tpr = cols / kVec;
-  const int rpb = kBlock / min(tpr, kBlock);
-  const long long row_blocks = (rows + rpb - 1) / rpb;
   const long long g = max(256LL, min(512LL, rows / 64));
-  return (int)max(1LL, min(row_blocks, g));
+  return (int)max(1LL, min(bn_row_blocks(rows, cols), g));
 }
 
+// Scratch of one chain: the slab [G][2C], then the per-channel
+// coefficients, [C] each: scale, shift forward; c1, c2, c3 backward.
 long long bn_scratch_floats(long long rows, int cols) {
   return (long long)bn_reduce_blocks(rows, cols) * 2 * cols + 3LL * cols;
+}
+static float* bn_scratch_coef(float* scratch, int G, int cols) {
+  return scratch + (size_t)G * 2 * cols;
+}
+
+static void bn_finalize(const float* slab, int G, const float* gamma,
+                        const float* beta, float* running_mean,
+                        float* running_var, float* save_mean,
+                        float* save_rstd, float* coef, long long rows,
+                        int cols, float momentum, float eps, bool training,
+                        hipStream_t stream) {
+  hipLaunchKernelGGL(bn_finalize_k, dim3(cols / kFinCh), dim3(kBlock), 0,
+                     stream, slab, G, gamma, beta, running_mean,
+                     running_var, save_mean, save_rstd, coef, coef + cols,
+                     rows, cols, momentum, eps, (int)training);
+}
+
+// Statistics (training only) and finalize over scratch; returns the
+// coefficients: scale [C], then shift [C].
+static float* bn_stats_finalize(const short* x, const float* gamma,
+                                const float* beta, float* running_mean,
+                                float* running_var, float* save_mean,
+                                float* save_rstd, float* scratch,
+                                long long rows, int cols, float momentum,
+                                float eps, bool training,
+                                hipStream_t stream) {
+  const int G = bn_reduce_blocks(rows, cols);
+  if (training)
+    hipLaunchKernelGGL(bn_stats_k<kUnroll>, dim3(G), dim3(kBlock), 0,
+                       stream, x, scratch, rows, cols);
+  float* coef = bn_scratch_coef(scratch, G, cols);
+  bn_finalize(scratch, G, gamma, beta, running_mean, running_var,
+              save_mean, save_rstd, coef, rows, cols, momentum, eps,
+              training, stream);
+  return coef;
+}
+
+static void bn_apply(const short* x, const short* res, const float* coef,
+                     short* y, unsigned char* mask, long long rows,
+                     int cols, bool relu, hipStream_t stream) {
+  auto ap = relu ? (res ? bn_apply_k<true, true> : bn_apply_k<true, false>)
+                 : (res ? bn_apply_k<false, true>
+                        : bn_apply_k<false, false>);
+  hipLaunchKernelGGL(ap, dim3(bn_grid(rows, cols)), dim3(kBlock), 0, stream,
+                     x, res, coef, coef + cols, y, mask, rows, cols);
+}
+
+// What a source is made of (Src::make), as the launchers hold it.
+struct BnSrcArgs {
+  const unsigned char* bytes;
+  const short* ga;
+  const short* gb;
+  short* s;
+  PoolGeom g;
+};
+
+// reduce over source RSrc of r -> finalize -> apply (the kernel ak,
+// over its source of a).
+template <class RSrc, class ApplyK>
+static void bn_bwd_chain(const short* x, const BnSrcArgs& r,
+                         const BnSrcArgs& a, ApplyK ak, const float* gamma,
+                         const float* save_mean, const float* save_rstd,
+                         float* scratch, float* dgamma, float* dbeta,
+                         short* dx, short* dres, long long rows, int cols,
+                         bool training, hipStream_t stream) {
+  const int G = bn_reduce_blocks(rows, cols);
+  hipLaunchKernelGGL((bn_bwd_reduce_k<RSrc, kUnroll>), dim3(G),
+                     dim3(kBlock), 0, stream, x, r.bytes, r.ga, r.gb,
+                     r.s, r.g, save_mean, save_rstd, scratch, rows, cols);
+  float* c1 = bn_scratch_coef(scratch, G, cols);
+  float* c2 = c1 + cols;
+  float* c3 = c2 + cols;
+  hipLaunchKernelGGL(bn_bwd_finalize_k, dim3(cols / kFinCh), dim3(kBlock),
+                     0, stream, scratch, G, gamma, save_rstd, dgamma, dbeta,
+                     c1, c2, c3, rows, cols, (int)training);
+  hipLaunchKernelGGL(ak, dim3(bn_grid(rows, cols)), dim3(kBlock), 0, stream,
+                     x, a.bytes, a.ga, a.gb, a.s, a.g, save_mean, save_rstd,
+                     c1, c2, c3, dx, dres, rows, cols);
 }
 
 void launch_bn_fwd(const short* x, const short* res, const float* gamma,
@@ -904,23 +863,10 @@ void launch_bn_fwd(const short* x, const short* res, const float* gamma,
                    float* scratch, short* y, unsigned char* mask,
                    long long rows, int cols, float momentum, float eps,
                    bool training, bool relu, hipStream_t stream) {
-  const int grid = bn_grid(rows, cols);
-  const int G = bn_reduce_blocks(rows, cols);
-  if (training)
-    hipLaunchKernelGGL(bn_stats_k<kUnroll>, dim3(G), dim3(kBlock), 0,
-                       stream, x, scratch, rows, cols);
-  // scratch: slab [G][2C], then scale [C], shift [C]
-  float* scale = scratch + (size_t)G * 2 * cols;
-  float* shift = scale + cols;
-  hipLaunchKernelGGL(bn_finalize_k, dim3(cols / kFinCh), dim3(kBlock), 0,
-                     stream, scratch, G, gamma, beta, running_mean,
-                     running_var, save_mean, save_rstd, scale, shift, rows,
-                     cols, momentum, eps, (int)training);
-  auto ap = relu ? (res ? bn_apply_k<true, true> : bn_apply_k<true, false>)
-                 : (res ? bn_apply_k<false, true>
-                        : bn_apply_k<false, false>);
-  hipLaunchKernelGGL(ap, dim3(grid), dim3(kBlock), 0, stream, x, res,
-                     scale, shift, y, mask, rows, cols);
+  const float* coef = bn_stats_finalize(
+      x, gamma, beta, running_mean, running_var, save_mean, save_rstd,
+      scratch, rows, cols, momentum, eps, training, stream);
+  bn_apply(x, res, coef, y, mask, rows, cols, relu, stream);
 }
 
 void launch_bn_fwd_slab(const short* x, const short* res,
@@ -931,18 +877,10 @@ void launch_bn_fwd_slab(const short* x, const short* res,
                         unsigned char* mask, long long rows, int cols,
                         float momentum, float eps, bool relu,
                         hipStream_t stream) {
-  // the slab's G rows come from the caller's kernel; coef: scale, shift
-  float* scale = coef;
-  float* shift = coef + cols;
-  hipLaunchKernelGGL(bn_finalize_k, dim3(cols / kFinCh), dim3(kBlock), 0,
-                     stream, slab, G, gamma, beta, running_mean,
-                     running_var, save_mean, save_rstd, scale, shift, rows,
-                     cols, momentum, eps, 1);
-  auto ap = relu ? (res ? bn_apply_k<true, true> : bn_apply_k<true, false>)
-                 : (res ? bn_apply_k<false, true>
-                        : bn_apply_k<false, false>);
-  hipLaunchKernelGGL(ap, dim3(bn_grid(rows, cols)), dim3(kBlock), 0, stream,
-                     x, res, scale, shift, y, mask, rows, cols);
+  // the slab's G rows come from the caller's kernel
+  bn_finalize(slab, G, gamma, beta, running_mean, running_var, save_mean,
+              save_rstd, coef, rows, cols, momentum, eps, true, stream);
+  bn_apply(x, res, coef, y, mask, rows, cols, relu, stream);
 }
 
 void launch_bn_bwd(const short* x, const unsigned char* mask,
@@ -951,26 +889,16 @@ void launch_bn_bwd(const short* x, const unsigned char* mask,
                    float* scratch, float* dgamma, float* dbeta, short* dx,
                    short* dres, long long rows, int cols, bool training,
                    bool relu, hipStream_t stream) {
-  const int grid = bn_grid(rows, cols);
-  const int G = bn_reduce_blocks(rows, cols);
-  auto rk = relu ? bn_bwd_reduce_k<true, kUnroll>
-                 : bn_bwd_reduce_k<false, kUnroll>;
-  hipLaunchKernelGGL(rk, dim3(G), dim3(kBlock), 0, stream, x, mask, dy,
-                     save_mean, save_rstd, scratch, rows, cols);
-  // scratch: slab [G][2C], then c1, c2, c3 [C] each
-  float* c1 = scratch + (size_t)G * 2 * cols;
-  float* c2 = c1 + cols;
-  float* c3 = c2 + cols;
-  hipLaunchKernelGGL(bn_bwd_finalize_k, dim3(cols / kFinCh), dim3(kBlock),
-                     0, stream, scratch, G, gamma, save_rstd, dgamma, dbeta,
-                     c1, c2, c3, rows, cols, (int)training);
-  auto ak = relu ? (dres ? bn_bwd_apply_k<true, true>
-                         : bn_bwd_apply_k<true, false>)
-                 : (dres ? bn_bwd_apply_k<false, true>
-                         : bn_bwd_apply_k<false, false>);
-  hipLaunchKernelGGL(ak, dim3(grid), dim3(kBlock), 0, stream, x, mask, dy,
-                     save_mean, save_rstd, c1, c2, c3, dx, dres, rows,
-                     cols);
+  const BnSrcArgs a{mask, dy, nullptr, nullptr, {}};
+  auto run = [&](auto src) {
+    using S = decltype(src);
+    bn_bwd_chain<S>(x, a, a, dres ? bn_bwd_apply_k<S, true>
+                                   : bn_bwd_apply_k<S, false>,
+                    gamma, save_mean, save_rstd, scratch, dgamma, dbeta, dx,
+                    dres, rows, cols, training, stream);
+  };
+  if (relu) run(DySrc<true>{});
+  else run(DySrc<false>{});
 }
 
 void launch_bn_bwd2(const short* x, const unsigned char* mask,
@@ -979,22 +907,18 @@ void launch_bn_bwd2(const short* x, const unsigned char* mask,
                     float* scratch, float* dgamma, float* dbeta, short* dx,
                     short* s, long long rows, int cols, bool training,
                     bool relu, hipStream_t stream) {
-  const int grid = bn_grid(rows, cols);
-  const int G = bn_reduce_blocks(rows, cols);
-  auto rk = relu ? bn_bwd2_reduce_k<true, kUnroll>
-                 : bn_bwd2_reduce_k<false, kUnroll>;
-  hipLaunchKernelGGL(rk, dim3(G), dim3(kBlock), 0, stream, x, mask, dya,
-                     dyb, save_mean, save_rstd, s, scratch, rows, cols);
-  // scratch: slab [G][2C], then c1, c2, c3 [C] each
-  float* c1 = scratch + (size_t)G * 2 * cols;
-  float* c2 = c1 + cols;
-  float* c3 = c2 + cols;
-  hipLaunchKernelGGL(bn_bwd_finalize_k, dim3(cols / kFinCh), dim3(kBlock),
-                     0, stream, scratch, G, gamma, save_rstd, dgamma, dbeta,
-                     c1, c2, c3, rows, cols, (int)training);
-  hipLaunchKernelGGL(bn_bwd2_apply_k, dim3(grid), dim3(kBlock), 0, stream,
-                     x, s, save_mean, save_rstd, c1, c2, c3, dx, rows,
-                     cols);
+  // the apply reads s, already masked, as its dy and stores no dres
+  using A = DySrc<false>;
+  const BnSrcArgs r{mask, dya, dyb, s, {}};
+  const BnSrcArgs a{nullptr, s, nullptr, nullptr, {}};
+  auto run = [&](auto src) {
+    bn_bwd_chain<decltype(src)>(x, r, a, bn_bwd_apply_k<A, false>, gamma,
+                                save_mean, save_rstd, scratch, dgamma,
+                                dbeta, dx, nullptr, rows, cols, training,
+                                stream);
+  };
+  if (relu) run(SumSrc<true>{});
+  else run(SumSrc<false>{});
 }
 
 void launch_bn_pool_fwd(const short* x, const float* gamma,
@@ -1007,20 +931,12 @@ void launch_bn_pool_fwd(const short* x, const float* gamma,
   const PoolGeom g{h, w, (h - 1) / 2 + 1, (w - 1) / 2 + 1};
   const long long rows = (long long)n * h * w;
   const long long orows = (long long)n * g.Ho * g.Wo;
-  const int G = bn_reduce_blocks(rows, cols);
-  if (training)
-    hipLaunchKernelGGL(bn_stats_k<kUnroll>, dim3(G), dim3(kBlock), 0,
-                       stream, x, scratch, rows, cols);
-  // scratch: slab [G][2C], then scale [C], shift [C]
-  float* scale = scratch + (size_t)G * 2 * cols;
-  float* shift = scale + cols;
-  hipLaunchKernelGGL(bn_finalize_k, dim3(cols / kFinCh), dim3(kBlock), 0,
-                     stream, scratch, G, gamma, beta, running_mean,
-                     running_var, save_mean, save_rstd, scale, shift, rows,
-                     cols, momentum, eps, (int)training);
+  const float* coef = bn_stats_finalize(
+      x, gamma, beta, running_mean, running_var, save_mean, save_rstd,
+      scratch, rows, cols, momentum, eps, training, stream);
   hipLaunchKernelGGL(bn_apply_pool_k, dim3(bn_grid(orows, cols)),
-                     dim3(kBlock), 0, stream, x, scale, shift, pooled, code,
-                     orows, cols, g);
+                     dim3(kBlock), 0, stream, x, coef, coef + cols, pooled,
+                     code, orows, cols, g);
 }
 
 void launch_bn_pool_bwd(const short* x, const unsigned char* code,
@@ -1031,18 +947,8 @@ void launch_bn_pool_bwd(const short* x, const unsigned char* code,
                         bool training, hipStream_t stream) {
   const PoolGeom g{h, w, (h - 1) / 2 + 1, (w - 1) / 2 + 1};
   const long long rows = (long long)n * h * w;
-  const int G = bn_reduce_blocks(rows, cols);
-  hipLaunchKernelGGL(bn_pool_bwd_reduce_k<kUnroll>, dim3(G), dim3(kBlock),
-                     0, stream, x, code, dyp, save_mean, save_rstd, scratch,
-                     rows, cols, g);
-  // scratch: slab [G][2C], then c1, c2, c3 [C] each
-  float* c1 = scratch + (size_t)G * 2 * cols;
-  float* c2 = c1 + cols;
-  float* c3 = c2 + cols;
-  hipLaunchKernelGGL(bn_bwd_finalize_k, dim3(cols / kFinCh), dim3(kBlock),
-                     0, stream, scratch, G, gamma, save_rstd, dgamma, dbeta,
-                     c1, c2, c3, rows, cols, (int)training);
-  hipLaunchKernelGGL(bn_pool_bwd_apply_k, dim3(bn_grid(rows, cols)),
-                     dim3(kBlock), 0, stream, x, code, dyp, save_mean,
-                     save_rstd, c1, c2, c3, dx, rows, cols, g);
+  const BnSrcArgs a{code, dyp, nullptr, nullptr, g};
+  bn_bwd_chain<PoolSrc>(x, a, a, bn_bwd_apply_k<PoolSrc, false>, gamma,
+                        save_mean, save_rstd, scratch, dgamma, dbeta, dx,
+                        nullptr, rows, cols, training, stream);
 }

@@ -151,6 +151,57 @@ std::vector<at::Tensor> layernorm_bwd(const at::Tensor& x,
 // BatchNorm (+add) (+ReLU), NHWC bf16
 // ---------------------------------------------------------------------
 
+// Shared validation; returns {rows, cols} of x. chan: the per-channel
+// tensors of the call. act: its tensors of x's shape, null where an
+// optional one is absent. With relu, mask is the forward's bit mask.
+static std::pair<long long, int> bn_check(
+    const char* op, const at::Tensor& x,
+    std::initializer_list<const at::Tensor*> chan,
+    std::initializer_list<const at::Tensor*> act, bool relu = false,
+    const at::Tensor* mask = nullptr) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
+                  x.is_contiguous() && x.dim() >= 1,
+              op, ": x must be a contiguous bf16 GPU tensor");
+  const int64_t cols = x.size(-1);
+  TORCH_CHECK(cols > 0 && cols % 8 == 0 && cols <= 2048, op,
+              " requires cols%8==0 and cols<=2048 (NHWC channels), got ",
+              cols);
+  for (const at::Tensor* t : chan)
+    TORCH_CHECK(t->is_cuda() && t->device() == x.device() &&
+                    t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                    t->numel() == cols,
+                op, ": per-channel tensors must be contiguous fp32 of ",
+                cols, " elements on x's device");
+  for (const at::Tensor* t : act)
+    TORCH_CHECK(!t || (t->is_cuda() && t->device() == x.device() &&
+                       t->scalar_type() == at::kBFloat16 &&
+                       t->is_contiguous() && t->sizes() == x.sizes()),
+                op, ": activations and gradients must be contiguous bf16 ",
+                x.sizes(), " on x's device");
+  TORCH_CHECK(!relu || (mask->is_cuda() && mask->device() == x.device() &&
+                        mask->scalar_type() == at::kByte &&
+                        mask->is_contiguous() &&
+                        mask->numel() == x.numel() / 8),
+              op, ": relu backward needs the forward's activation mask, "
+              "contiguous uint8 of ", x.numel() / 8,
+              " elements on x's device");
+  return {x.numel() / cols, (int)cols};
+}
+
+static const at::Tensor* opt_ptr(const c10::optional<at::Tensor>& t) {
+  return t.has_value() ? &t.value() : nullptr;
+}
+
+// With relu the forward packs 1 bit per element, which backward uses
+// instead of re-reading y; without, the mask is empty and not touched.
+static at::Tensor bn_alloc_mask(const at::Tensor& x, bool relu) {
+  return at::empty({relu ? x.numel() / 8 : 0},
+                   x.options().dtype(at::kByte));
+}
+static unsigned char* mask_ptr(const at::Tensor& mask, bool relu) {
+  return relu ? mask.data_ptr<unsigned char>() : nullptr;
+}
+
 std::vector<at::Tensor> bn_fwd(const at::Tensor& x,
                                const c10::optional<at::Tensor>& res,
                                const at::Tensor& gamma,
@@ -158,41 +209,24 @@ std::vector<at::Tensor> bn_fwd(const at::Tensor& x,
                                at::Tensor running_mean,
                                at::Tensor running_var, double momentum,
                                double eps, bool training, bool relu) {
-  CHECK_BF16_CUDA(x);
-  CHECK_F32_CUDA(gamma);
-  CHECK_F32_CUDA(beta);
+  const auto [rows, cols] = bn_check(
+      "bn_fwd", x, {&gamma, &beta, &running_mean, &running_var},
+      {opt_ptr(res)});
   DeviceGuard guard(x.device());
-  const int cols = (int)x.size(-1);
-  const long long rows = x.numel() / cols;
-  TORCH_CHECK(cols % 8 == 0 && cols <= 2048,
-              "bn_fwd requires cols%8==0 and cols<=2048 (NHWC channels)");
-  const short* res_ptr = nullptr;
-  if (res.has_value()) {
-    CHECK_BF16_CUDA(res.value());
-    TORCH_CHECK(res->sizes() == x.sizes());
-    res_ptr = bf_ptr(res.value());
-  }
   auto f32 = x.options().dtype(at::kFloat);
   auto y = at::empty_like(x);
   auto save_mean = at::empty({cols}, f32);
   auto save_rstd = at::empty({cols}, f32);
   // partial-sum slab + coefficients; fully written before it is read
   auto scratch = at::empty({bn_scratch_floats(rows, cols)}, f32);
-  at::Tensor mask;
-  unsigned char* mask_ptr = nullptr;
-  if (relu) {
-    // 1 bit per element: backward uses this instead of re-reading y
-    mask = at::empty({rows * cols / 8}, x.options().dtype(at::kByte));
-    mask_ptr = mask.data_ptr<unsigned char>();
-  } else {
-    mask = at::empty({0}, x.options().dtype(at::kByte));
-  }
-  launch_bn_fwd(bf_ptr(x), res_ptr, gamma.data_ptr<float>(),
-                beta.data_ptr<float>(), running_mean.data_ptr<float>(),
+  auto mask = bn_alloc_mask(x, relu);
+  launch_bn_fwd(bf_ptr(x), res ? bf_ptr(*res) : nullptr,
+                gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                running_mean.data_ptr<float>(),
                 running_var.data_ptr<float>(), save_mean.data_ptr<float>(),
                 save_rstd.data_ptr<float>(), scratch.data_ptr<float>(),
-                bf_ptr_mut(y), mask_ptr, rows, cols, (float)momentum,
-                (float)eps, training, relu, cur_stream());
+                bf_ptr_mut(y), mask_ptr(mask, relu), rows, cols,
+                (float)momentum, (float)eps, training, relu, cur_stream());
   return {y, save_mean, save_rstd, mask};
 }
 
@@ -206,50 +240,30 @@ std::vector<at::Tensor> bn_fwd_slab(const at::Tensor& x,
                                     at::Tensor running_mean,
                                     at::Tensor running_var, double momentum,
                                     double eps, bool relu) {
-  CHECK_BF16_CUDA(x);
+  const auto [rows, cols] = bn_check(
+      "bn_fwd_slab", x, {&gamma, &beta, &running_mean, &running_var},
+      {opt_ptr(res)});
   CHECK_F32_CUDA(slab);
-  CHECK_F32_CUDA(gamma);
-  CHECK_F32_CUDA(beta);
-  CHECK_F32_CUDA(running_mean);
-  CHECK_F32_CUDA(running_var);
-  DeviceGuard guard(x.device());
-  const int cols = (int)x.size(-1);
-  const long long rows = x.numel() / cols;
-  TORCH_CHECK(cols % 8 == 0 && cols <= 2048,
-              "bn_fwd_slab requires cols%8==0 and cols<=2048");
   TORCH_CHECK(slab.dim() == 2 && slab.size(0) >= 1 &&
                   slab.size(1) == 2 * (int64_t)cols &&
                   slab.device() == x.device(),
               "bn_fwd_slab: slab must be [G, 2*cols] on x's device");
-  TORCH_CHECK(gamma.numel() == cols && beta.numel() == cols &&
-              running_mean.numel() == cols && running_var.numel() == cols);
-  const short* res_ptr = nullptr;
-  if (res.has_value()) {
-    CHECK_BF16_CUDA(res.value());
-    TORCH_CHECK(res->sizes() == x.sizes());
-    res_ptr = bf_ptr(res.value());
-  }
+  DeviceGuard guard(x.device());
   auto f32 = x.options().dtype(at::kFloat);
   auto y = at::empty_like(x);
   auto save_mean = at::empty({cols}, f32);
   auto save_rstd = at::empty({cols}, f32);
   auto coef = at::empty({2 * (int64_t)cols}, f32);
-  at::Tensor mask;
-  unsigned char* mask_ptr = nullptr;
-  if (relu) {
-    mask = at::empty({rows * cols / 8}, x.options().dtype(at::kByte));
-    mask_ptr = mask.data_ptr<unsigned char>();
-  } else {
-    mask = at::empty({0}, x.options().dtype(at::kByte));
-  }
-  launch_bn_fwd_slab(bf_ptr(x), res_ptr, slab.data_ptr<float>(),
-                     (int)slab.size(0), gamma.data_ptr<float>(),
-                     beta.data_ptr<float>(), running_mean.data_ptr<float>(),
+  auto mask = bn_alloc_mask(x, relu);
+  launch_bn_fwd_slab(bf_ptr(x), res ? bf_ptr(*res) : nullptr,
+                     slab.data_ptr<float>(), (int)slab.size(0),
+                     gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                     running_mean.data_ptr<float>(),
                      running_var.data_ptr<float>(),
                      save_mean.data_ptr<float>(),
                      save_rstd.data_ptr<float>(), coef.data_ptr<float>(),
-                     bf_ptr_mut(y), mask_ptr, rows, cols, (float)momentum,
-                     (float)eps, relu, cur_stream());
+                     bf_ptr_mut(y), mask_ptr(mask, relu), rows, cols,
+                     (float)momentum, (float)eps, relu, cur_stream());
   return {y, save_mean, save_rstd, mask};
 }
 
@@ -260,14 +274,9 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& x,
                                const at::Tensor& save_mean,
                                const at::Tensor& save_rstd, bool training,
                                bool relu, bool needs_dres) {
-  CHECK_BF16_CUDA(x);
-  CHECK_BF16_CUDA(dy);
-  CHECK_F32_CUDA(gamma);
+  const auto [rows, cols] = bn_check(
+      "bn_bwd", x, {&gamma, &save_mean, &save_rstd}, {&dy}, relu, &mask);
   DeviceGuard guard(x.device());
-  const int cols = (int)x.size(-1);
-  const long long rows = x.numel() / cols;
-  TORCH_CHECK(!relu || mask.numel() == rows * cols / 8,
-              "relu backward needs the forward's activation mask");
   auto f32 = x.options().dtype(at::kFloat);
   auto dx = at::empty_like(x);
   auto dgamma = at::empty({cols}, f32);
@@ -279,9 +288,8 @@ std::vector<at::Tensor> bn_bwd(const at::Tensor& x,
     dres = at::empty_like(x);
     dres_ptr = bf_ptr_mut(dres);
   }
-  launch_bn_bwd(bf_ptr(x),
-                relu ? mask.data_ptr<unsigned char>() : nullptr,
-                bf_ptr(dy), gamma.data_ptr<float>(),
+  launch_bn_bwd(bf_ptr(x), mask_ptr(mask, relu), bf_ptr(dy),
+                gamma.data_ptr<float>(),
                 save_mean.data_ptr<float>(), save_rstd.data_ptr<float>(),
                 scratch.data_ptr<float>(), dgamma.data_ptr<float>(),
                 dbeta.data_ptr<float>(), bf_ptr_mut(dx), dres_ptr, rows,
@@ -301,30 +309,18 @@ std::vector<at::Tensor> bn_bwd2(const at::Tensor& x,
                                 const at::Tensor& save_mean,
                                 const at::Tensor& save_rstd, bool training,
                                 bool relu) {
-  CHECK_BF16_CUDA(x);
-  CHECK_BF16_CUDA(dy_a);
-  CHECK_BF16_CUDA(dy_b);
-  CHECK_F32_CUDA(gamma);
-  TORCH_CHECK(dy_a.sizes() == x.sizes() && dy_b.sizes() == x.sizes(),
-              "bn_bwd2: both gradients must have x's shape");
+  const auto [rows, cols] =
+      bn_check("bn_bwd2", x, {&gamma, &save_mean, &save_rstd},
+               {&dy_a, &dy_b}, relu, &mask);
   DeviceGuard guard(x.device());
-  const int cols = (int)x.size(-1);
-  const long long rows = x.numel() / cols;
-  TORCH_CHECK(cols % 8 == 0 && cols <= 2048,
-              "bn_bwd2 requires cols%8==0 and cols<=2048 (NHWC channels)");
-  TORCH_CHECK(!relu || mask.numel() == rows * cols / 8,
-              "relu backward needs the forward's activation mask");
-  TORCH_CHECK(gamma.numel() == cols && save_mean.numel() == cols &&
-              save_rstd.numel() == cols);
   auto f32 = x.options().dtype(at::kFloat);
   auto dx = at::empty_like(x);
   auto s = at::empty_like(x);
   auto dgamma = at::empty({cols}, f32);
   auto dbeta = at::empty({cols}, f32);
   auto scratch = at::empty({bn_scratch_floats(rows, cols)}, f32);
-  launch_bn_bwd2(bf_ptr(x),
-                 relu ? mask.data_ptr<unsigned char>() : nullptr,
-                 bf_ptr(dy_a), bf_ptr(dy_b), gamma.data_ptr<float>(),
+  launch_bn_bwd2(bf_ptr(x), mask_ptr(mask, relu), bf_ptr(dy_a),
+                 bf_ptr(dy_b), gamma.data_ptr<float>(),
                  save_mean.data_ptr<float>(), save_rstd.data_ptr<float>(),
                  scratch.data_ptr<float>(), dgamma.data_ptr<float>(),
                  dbeta.data_ptr<float>(), bf_ptr_mut(dx), bf_ptr_mut(s),
@@ -339,21 +335,14 @@ std::vector<at::Tensor> bn_pool_fwd(const at::Tensor& x,
                                     at::Tensor running_mean,
                                     at::Tensor running_var, double momentum,
                                     double eps, bool training) {
-  CHECK_BF16_CUDA(x);
-  CHECK_F32_CUDA(gamma);
-  CHECK_F32_CUDA(beta);
-  CHECK_F32_CUDA(running_mean);
-  CHECK_F32_CUDA(running_var);
+  const int cols = bn_check("bn_pool_fwd", x,
+                            {&gamma, &beta, &running_mean, &running_var},
+                            {}).second;
   TORCH_CHECK(x.dim() == 4, "bn_pool_fwd takes x as [N,H,W,C]");
   DeviceGuard guard(x.device());
   const int64_t n = x.size(0), h = x.size(1), w = x.size(2);
-  const int cols = (int)x.size(3);
-  TORCH_CHECK(cols % 8 == 0 && cols <= 2048,
-              "bn_pool_fwd requires cols%8==0 and cols<=2048");
   TORCH_CHECK(n > 0 && h > 0 && w > 0 && n * h * w < (1LL << 31),
               "bn_pool_fwd requires 0 < N*H*W < 2^31");
-  TORCH_CHECK(gamma.numel() == cols && beta.numel() == cols &&
-              running_mean.numel() == cols && running_var.numel() == cols);
   const int64_t ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
   auto f32 = x.options().dtype(at::kFloat);
   auto pooled = at::empty({n, ho, wo, cols}, x.options());
@@ -379,29 +368,23 @@ std::vector<at::Tensor> bn_pool_bwd(const at::Tensor& x,
                                     const at::Tensor& save_mean,
                                     const at::Tensor& save_rstd,
                                     bool training) {
-  CHECK_BF16_CUDA(x);
+  const int cols = bn_check("bn_pool_bwd", x,
+                            {&gamma, &save_mean, &save_rstd}, {}).second;
   CHECK_BF16_CUDA(dyp);
-  CHECK_F32_CUDA(gamma);
-  CHECK_F32_CUDA(save_mean);
-  CHECK_F32_CUDA(save_rstd);
   TORCH_CHECK(x.dim() == 4, "bn_pool_bwd takes x as [N,H,W,C]");
   DeviceGuard guard(x.device());
   const int64_t n = x.size(0), h = x.size(1), w = x.size(2);
-  const int cols = (int)x.size(3);
-  TORCH_CHECK(cols % 8 == 0 && cols <= 2048,
-              "bn_pool_bwd requires cols%8==0 and cols<=2048");
   TORCH_CHECK(n > 0 && h > 0 && w > 0 && n * h * w < (1LL << 31),
               "bn_pool_bwd requires 0 < N*H*W < 2^31");
   const int64_t ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
   const std::vector<int64_t> pshape = {n, ho, wo, (int64_t)cols};
-  TORCH_CHECK(dyp.sizes() == at::IntArrayRef(pshape),
-              "pooled grad must be [N,Ho,Wo,C]");
-  TORCH_CHECK(code.is_cuda() && code.scalar_type() == at::kByte &&
-              code.is_contiguous() &&
+  TORCH_CHECK(dyp.sizes() == at::IntArrayRef(pshape) &&
+                  dyp.device() == x.device(),
+              "pooled grad must be [N,Ho,Wo,C] on x's device");
+  TORCH_CHECK(code.is_cuda() && code.device() == x.device() &&
+              code.scalar_type() == at::kByte && code.is_contiguous() &&
               code.sizes() == at::IntArrayRef(pshape),
               "backward needs the forward's tap codes");
-  TORCH_CHECK(gamma.numel() == cols && save_mean.numel() == cols &&
-              save_rstd.numel() == cols);
   auto f32 = x.options().dtype(at::kFloat);
   auto dx = at::empty_like(x);
   auto dgamma = at::empty({cols}, f32);

@@ -176,3 +176,73 @@ def test_bn_reduce_bitwise_reproducible(shape):
     a, b = run(), run()
     for k in a:
         assert torch.equal(a[k], b[k]), k
+
+
+def test_bad_arguments_are_refused():
+    """The bindings refuse, before any launch, tensors that the kernels
+    would read or write out of bounds; a valid call at the same shape
+    still runs afterwards and matches the fp32 reference."""
+    C = ops.ext()
+    torch.manual_seed(3)
+    ch = 8
+    x = torch.randn(1, 2, 2, ch, device="cuda").bfloat16()   # [N,H,W,C]
+    dy = torch.randn_like(x)
+    gamma = torch.rand(ch, device="cuda") + 0.5
+    beta = torch.randn(ch, device="cuda")
+    mean = torch.zeros(ch, device="cuda")
+    rstd = torch.ones(ch, device="cuda")
+    mask = torch.zeros(x.numel() // 8, device="cuda", dtype=torch.uint8)
+    wide = torch.ones(16, device="cuda")
+
+    def bwd(dy=dy, mean=mean, rstd=rstd, mask=mask, relu=False):
+        return C.bn_bwd(x, mask, dy, gamma, mean, rstd, True, relu, False)
+
+    def fwd(x=x, rm=None):
+        rm = torch.zeros(ch, device="cuda") if rm is None else rm
+        rv = torch.ones(ch, device="cuda")
+        return C.bn_fwd(x, None, gamma, beta, rm, rv, 0.1, 1e-5, True,
+                        False)
+
+    # each with the start of the shared validation's message, so that
+    # the refusal is known to come from there and not from later on
+    bad = [
+        (lambda: bwd(dy=torch.zeros(1, 2, 2, 16, device="cuda",
+                                    dtype=torch.bfloat16)),
+         "bn_bwd: activations and gradients"),
+        (lambda: bwd(mean=wide), "bn_bwd: per-channel tensors"),
+        (lambda: bwd(rstd=rstd.double()), "bn_bwd: per-channel tensors"),
+        (lambda: bwd(relu=True, mask=mask[:-1]), "bn_bwd: relu backward"),
+        (lambda: bwd(relu=True, mask=mask.cpu()), "bn_bwd: relu backward"),
+        (lambda: fwd(rm=wide), "bn_fwd: per-channel tensors"),
+        (lambda: fwd(x=torch.zeros(1, 2, 2, 12, device="cuda",
+                                   dtype=torch.bfloat16)),
+         "bn_fwd requires cols%8==0"),
+    ]
+    for call, message in bad:
+        with pytest.raises(RuntimeError, match=message):
+            call()
+
+    rm = torch.zeros(ch, device="cuda")
+    rv = torch.ones(ch, device="cuda")
+    y, save_mean, save_rstd, _ = C.bn_fwd(x, None, gamma, beta, rm, rv, 0.1,
+                                          1e-5, True, False)
+    dx, dgamma, dbeta = bwd(mean=save_mean, rstd=save_rstd)
+
+    # channels-first views of the NHWC tensors for the reference
+    xr = x.float().permute(0, 3, 1, 2).requires_grad_(True)
+    gr = gamma.clone().requires_grad_(True)
+    br = beta.clone().requires_grad_(True)
+    rm_r = torch.zeros(ch, device="cuda")
+    rv_r = torch.ones(ch, device="cuda")
+    yr = torch.nn.functional.batch_norm(xr, rm_r, rv_r, gr, br, True, 0.1,
+                                        1e-5)
+    yr.backward(dy.float().permute(0, 3, 1, 2))
+    nhw = x.numel() // ch
+    assert torch.allclose(y.float().permute(0, 3, 1, 2), yr.detach(),
+                          atol=5e-2, rtol=5e-2)
+    assert torch.allclose(rm, rm_r, atol=1e-2, rtol=1e-2)
+    assert torch.allclose(rv, rv_r, atol=1e-2, rtol=1e-2)
+    assert torch.allclose(dx.float().permute(0, 3, 1, 2), xr.grad,
+                          atol=5e-2, rtol=5e-2)
+    assert torch.allclose(dgamma, gr.grad, atol=2e-2 * nhw ** 0.5, rtol=2e-2)
+    assert torch.allclose(dbeta, br.grad, atol=2e-2 * nhw ** 0.5, rtol=2e-2)
