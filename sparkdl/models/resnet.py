@@ -14,7 +14,10 @@ scripts/probe_conv1x1_bn.py (profiles/probe_conv1x1_bn.log,
 profiles/README.md "Round 7"); their dgrad and wgrad stay on MIOpen, and
 SPARKDL_CONV1X1_STATS=0 restores the unfused route exactly. The all
 in-house 1x1 package (sparkdl.ops.Conv1x1 with SPARKDL_CONV1X1=1/all)
-stays opt-in. Every
+stays opt-in, and so does the hand-written 3x3 kernel: each
+bottleneck's conv2 is a sparkdl.ops.Conv3x3, an nn.Conv2d that with
+SPARKDL_CONV3X3=1 runs forward and dgrad of its 13 stride-1 instances on
+csrc/conv3x3.hip (wgrad on MIOpen) and unset is MIOpen as before. Every
 BatchNorm/ReLU/residual-add runs through sparkdl.ops' fused bf16-NHWC
 BatchNormAct2d kernels (SURVEY.md §2.2 N4/N5 — the conv-block epilogue
 fusion); the stem's BatchNorm + ReLU + 3x3/2 max-pool is one kernel chain
@@ -38,8 +41,8 @@ tensor; autograd adds there.
 import torch
 import torch.nn as nn
 
-from sparkdl.ops import (BatchNormAct2d, Conv1x1, batch_norm_relu_maxpool,
-                         conv1x1_bn_act)
+from sparkdl.ops import (BatchNormAct2d, Conv1x1, Conv3x3,
+                         batch_norm_relu_maxpool, conv1x1_bn_act)
 
 
 class Bottleneck(nn.Module):
@@ -50,8 +53,7 @@ class Bottleneck(nn.Module):
         cout = width * self.expansion
         self.conv1 = Conv1x1(cin, width)
         self.bn1 = BatchNormAct2d(width, relu=True)
-        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1,
-                               bias=False)
+        self.conv2 = Conv3x3(width, width, stride)
         self.bn2 = BatchNormAct2d(width, relu=True)
         self.conv3 = Conv1x1(width, cout)
         # bn3 fuses the residual add + final ReLU of the block

@@ -529,6 +529,52 @@ std::vector<int64_t> conv1x1_stats_plan_py(int64_t M, int64_t N, int64_t K,
 }
 
 // ---------------------------------------------------------------------
+// 3x3 stride-1 pad-1 convolution, NHWC bf16
+// ---------------------------------------------------------------------
+
+// y [N,H,W,Cout] = conv3x3(x [N,H,W,Cin], wt [Cout,3,3,Cin]), zero
+// padding, no bias. Also the data gradient, on dy and the flipped,
+// channel-swapped weight.
+at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wt,
+                   int64_t max_workers) {
+  CHECK_BF16_CUDA(x);
+  CHECK_BF16_CUDA(wt);
+  TORCH_CHECK(wt.device() == x.device(),
+              "conv3x3: x and wt must share one device");
+  TORCH_CHECK(x.dim() == 4 && wt.dim() == 4,
+              "conv3x3 takes x as [N,H,W,Cin] and wt as [Cout,3,3,Cin]");
+  TORCH_CHECK(wt.size(3) == x.size(3), "conv3x3: x has ", x.size(3),
+              " input channels, wt has ", wt.size(3));
+  TORCH_CHECK(wt.size(1) == 3 && wt.size(2) == 3,
+              "conv3x3 takes 3x3 taps, got ", wt.size(1), "x", wt.size(2));
+  const int64_t n = x.size(0), h = x.size(1), w = x.size(2);
+  const int64_t cin = x.size(3), cout = wt.size(0);
+  TORCH_CHECK(cin < (1 << 20) && cout < (1 << 20) &&
+                  conv3x3_supported(n, h, w, (int)cin, (int)cout),
+              "conv3x3 requires Cin and Cout multiples of 64, 1 <= W <= 56,"
+              " H >= 1 and N*H*W < 2^31, got x ", x.sizes(), " wt ",
+              wt.sizes());
+  TORCH_CHECK(max_workers >= 0 && max_workers < (1 << 20));
+  DeviceGuard guard(x.device());
+  auto y = at::empty({n, h, w, cout}, x.options());
+  launch_conv3x3(bf_ptr(x), bf_ptr(wt), bf_ptr_mut(y), (int)n, (int)h,
+                 (int)w, (int)cin, (int)cout, (int)max_workers,
+                 cur_stream());
+  return y;
+}
+
+std::vector<int64_t> conv3x3_plan_py(int64_t n, int64_t h, int64_t w,
+                                     int64_t cin, int64_t cout,
+                                     int64_t max_workers) {
+  TORCH_CHECK(cin < (1 << 20) && cout < (1 << 20) &&
+              conv3x3_supported(n, h, w, (int)cin, (int)cout));
+  int rows, imgs, tiles, workers;
+  conv3x3_plan((int)n, (int)h, (int)w, (int)cin, (int)cout,
+               (int)max_workers, &rows, &imgs, &tiles, &workers);
+  return {rows, imgs, tiles, workers};
+}
+
+// ---------------------------------------------------------------------
 // Flash attention (D=64)
 // ---------------------------------------------------------------------
 
@@ -880,6 +926,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(chunks per N-block, slab rows G) of a conv1x1_stats launch",
         py::arg("m"), py::arg("n"), py::arg("k"),
         py::arg("max_workers") = 0);
+  m.def("conv3x3", &conv3x3,
+        "3x3 stride-1 pad-1 convolution, NHWC bf16 (forward and dgrad)",
+        py::arg("x"), py::arg("wt"), py::arg("max_workers") = 0);
+  m.def("conv3x3_plan", &conv3x3_plan_py,
+        "(rows per band, images per tile, tiles and workers per N-block) "
+        "of a conv3x3 launch",
+        py::arg("n"), py::arg("h"), py::arg("w"), py::arg("cin"),
+        py::arg("cout"), py::arg("max_workers") = 0);
   m.def("bn_fwd_slab", &bn_fwd_slab,
         "Fused BatchNorm(+add)(+ReLU) fwd over pre-summed statistics");
   m.def("wgrad_splitk", &wgrad_splitk,

@@ -187,6 +187,23 @@ void launch_conv1x1_stats(const short* A, const short* W, short* C,
                           float* slab, long long M, int N, int K,
                           int max_workers, hipStream_t stream);
 
+// 3x3 stride-1 pad-1 convolution (csrc/conv3x3.hip), bf16 NHWC, fp32
+// accumulation, no bias: y[n,h,w,co] = sum x[n,h+kh-1,w+kw-1,ci] *
+// wt[co,kh,kw,ci], x [n,h,w,cin], wt [cout,3,3,cin], y [n,h,w,cout].
+// Forward and, on dy with flipped taps and swapped channel roles, dgrad.
+// Supported: cin and cout multiples of 64, 1 <= w <= 56, h >= 1,
+// n*h*w < 2^31. conv3x3_plan gives the tiling of a launch: output rows
+// per band and whole images per tile (one of the two is 1 unless an
+// image has at most 256 pixels), tiles per 64-wide N-block and
+// persistent workers per N-block; max_workers > 0 caps the workers.
+bool conv3x3_supported(long long n, long long h, long long w, int cin,
+                       int cout);
+void conv3x3_plan(int n, int h, int w, int cin, int cout, int max_workers,
+                  int* rows, int* imgs, int* tiles, int* workers);
+void launch_conv3x3(const short* x, const short* wt, short* y, int n, int h,
+                    int w, int cin, int cout, int max_workers,
+                    hipStream_t stream);
+
 // Split-M wgrad GEMM (dW = dZ^T @ X, M-major operands): blocked-LDS
 // tr_b16 fragment path, fp32 output with split atomics. Ships behind
 // SPARKDL_FUSED_WGRAD=1 (Tensile still measures faster).

@@ -1,6 +1,7 @@
 // Shared MFMA tile vocabulary for the bf16 GEMM and attention kernels
-// (gemm_gelu.hip, gemm_stream.hip, wgrad.hip, attention.hip): vector
-// types, lane -> fragment coordinates, the st_16x32 LDS swizzle, the
+// (gemm_gelu.hip, gemm_stream.hip, conv1x1_stats.hip, conv3x3.hip,
+// wgrad.hip, attention.hip): vector types, lane -> fragment
+// coordinates, the st_16x32 LDS swizzle, the
 // width-16 global_load_lds staging and the swizzled fragment read.
 // Device-only; every helper inlines to the arithmetic it names.
 //

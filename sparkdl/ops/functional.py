@@ -808,6 +808,79 @@ def conv1x1_bn_act(x, conv, bn, residual=None, fork=False):
     return bn(conv(x), residual=residual, fork=fork)
 
 
+# ---------------------------------------------------------------------------
+# 3x3 stride-1 pad-1 convolution (csrc/conv3x3.hip)
+# ---------------------------------------------------------------------------
+
+def conv3x3_supported(n, h, w, cin, cout):
+    """Shapes the conv3x3 kernel takes (mirror of csrc/conv3x3.hip)."""
+    return (cin >= 64 and cin % 64 == 0 and cout >= 64 and cout % 64 == 0
+            and n >= 1 and h >= 1 and 1 <= w <= 56 and n * h * w < 2 ** 31)
+
+
+def conv3x3_route(cin, cout, stride=1, mode=None):
+    """Whether a ``Conv3x3`` runs the in-house kernel (forward and dgrad)
+    on inputs that qualify. ``mode`` defaults to SPARKDL_CONV3X3, which
+    defaults to "0" (MIOpen): on only with ``mode != "0"``, stride 1 and
+    channel counts that are multiples of 64."""
+    if mode is None:
+        mode = os.environ.get("SPARKDL_CONV3X3", "0")
+    return (mode != "0" and stride == 1
+            and conv3x3_supported(1, 1, 1, cin, cout))
+
+
+class _Conv3x3Fn(torch.autograd.Function):
+    """y = conv2d(x, weight, padding=1) on channels_last bf16 tensors.
+    Forward and dgrad run the conv3x3 kernel, dgrad on dy with the taps
+    flipped and the channel roles swapped; wgrad is the library's.
+    channels_last [N,C,H,W] is [N,H,W,C] as a view, and a channels_last
+    weight [Cout,Cin,3,3] is the kernel's [Cout,3,3,Cin] as a view."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        C = _ops.ext()
+        ctx.save_for_backward(x, weight)
+        y = C.conv3x3(x.permute(0, 2, 3, 1),
+                      weight.permute(0, 2, 3, 1).contiguous(), 0)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy):
+        C = _ops.ext()
+        x, weight = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            # [Cout,Cin,kh,kw] -> [Cin, 2-kh, 2-kw, Cout]
+            wt = weight.flip(2, 3).permute(1, 2, 3, 0).contiguous()
+            dx = C.conv3x3(dy.permute(0, 2, 3, 1), wt, 0).permute(0, 3, 1, 2)
+        if ctx.needs_input_grad[1]:
+            dw = torch.ops.aten.convolution_backward(
+                dy, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0],
+                1, [False, True, False])[1]
+        return dx, dw
+
+
+def conv3x3(x, weight):
+    """``conv2d(x, weight, padding=1)`` for a 3x3 ``weight``
+    [Cout,Cin,3,3] and ``x`` [N,Cin,H,W].
+
+    bf16 channels_last GPU tensors of a supported shape (Cin and Cout
+    multiples of 64, W <= 56, N*H*W < 2^31) run the hand-written
+    implicit-GEMM kernel forward and for the data gradient; the weight
+    gradient is the library's. Everything else is
+    ``torch.nn.functional.conv2d(x, weight, padding=1)`` exactly."""
+    if (x.is_cuda and weight.is_cuda and x.dim() == 4 and weight.dim() == 4
+            and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
+            and tuple(weight.shape[2:]) == (3, 3)
+            and weight.shape[1] == x.shape[1]
+            and x.is_contiguous(memory_format=torch.channels_last)
+            and conv3x3_supported(x.shape[0], x.shape[2], x.shape[3],
+                                  x.shape[1], weight.shape[0])):
+        return _Conv3x3Fn.apply(x, weight)
+    return torch.nn.functional.conv2d(x, weight, padding=1)
+
+
 class _LinearFusedFn(torch.autograd.Function):
     """y = x @ W^T + b with the bias fused into the MFMA GEMM epilogue
     (act=0). dgrad runs on the same kernel via W^T; wgrad/dbias on

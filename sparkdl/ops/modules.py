@@ -6,7 +6,8 @@ SURVEY.md §7 hard part 4) while activations flow in bf16.
 GEMM with the bias(+GELU) epilogue fused in-kernel (default since round
 2; ``SPARKDL_FUSED_GEMM=0`` restores the library path).  ``Conv1x1``
 exposes the streaming tall-skinny GEMM for 1x1 convolutions (opt-in —
-see its docstring for the measured routing decision).
+see its docstring for the measured routing decision), ``Conv3x3`` the
+hand-written 3x3 stride-1 convolution (opt-in as well).
 """
 
 import torch
@@ -210,3 +211,29 @@ class Conv1x1(nn.Module):
 
     def extra_repr(self):
         return "%d, %d, stride=%d" % (self.cin, self.cout, self.stride)
+
+
+class Conv3x3(nn.Conv2d):
+    """3x3 convolution, padding 1, no bias (the ResNet
+    bottleneck's conv2). An ``nn.Conv2d`` in construction, parameters,
+    state-dict keys and default behaviour: ``forward`` is MIOpen's unless
+    ``functional.conv3x3_route`` says otherwise.
+
+    ``SPARKDL_CONV3X3=1`` moves the stride-1 instances with channel
+    counts that are multiples of 64 (13 of ResNet-50's 16) to the
+    hand-written implicit-GEMM kernel of csrc/conv3x3.hip for forward
+    and dgrad, on bf16 channels_last GPU inputs; wgrad stays on the
+    library. Opt-in: scripts/conv3x3_bench.py times the kernel against
+    MIOpen at the four ResNet-50 sites (profiles/conv3x3_sites.log;
+    profiles/README.md, "3x3 convolution kernel")."""
+
+    def __init__(self, cin, cout, stride=1):
+        super().__init__(cin, cout, 3, stride=stride, padding=1, bias=False)
+
+    def forward(self, x):
+        if (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
+                and x.is_contiguous(memory_format=torch.channels_last)
+                and F_.conv3x3_route(self.in_channels, self.out_channels,
+                                     self.stride[0])):
+            return F_.conv3x3(x, self.weight.to(x.dtype))
+        return super().forward(x)
