@@ -17,6 +17,15 @@ runs each as one kernel forward and one backward
 (``ops.dropout_add_layer_norm``) with no stored mask. It is opt-in
 because its dropout mask is the kernels' counter hash, not torch's
 Philox draw: the same seed then gives another training trajectory.
+
+The MLM loss is ``F.linear`` on the tied embedding, an eager bias add,
+a cast to fp32 and ``F.cross_entropy`` by default.
+``BertConfig(fused_mlm_loss=True)`` (or SPARKDL_FUSED_MLM_LOSS=1) makes
+``bert_pretrain_step`` call ``BertBase.mlm_loss``, which runs
+``ops.linear_cross_entropy``: the logits never reach memory. It is
+opt-in because the fused loss is computed from fp32 logits where the
+default path rounds them to bf16 first, so the same seed gives a
+slightly different trajectory.
 """
 
 import math
@@ -31,7 +40,7 @@ from sparkdl.ops import LayerNorm, Linear, LinearGelu
 class BertConfig:
     def __init__(self, vocab_size=30522, hidden=768, layers=12, heads=12,
                  ffn=3072, max_seq=512, type_vocab=2, dropout=0.1,
-                 fused_dropout_ln=None):
+                 fused_dropout_ln=None, fused_mlm_loss=None):
         self.vocab_size = vocab_size
         self.hidden = hidden
         self.layers = layers
@@ -45,6 +54,11 @@ class BertConfig:
             fused_dropout_ln = os.environ.get(
                 "SPARKDL_FUSED_DROPOUT_LN", "0") == "1"
         self.fused_dropout_ln = bool(fused_dropout_ln)
+        # None: SPARKDL_FUSED_MLM_LOSS ("1" = on); off by default
+        if fused_mlm_loss is None:
+            fused_mlm_loss = os.environ.get(
+                "SPARKDL_FUSED_MLM_LOSS", "0") == "1"
+        self.fused_mlm_loss = bool(fused_mlm_loss)
 
 
 class BertEmbeddings(nn.Module):
@@ -216,6 +230,24 @@ class BertBase(nn.Module):
         h = h.reshape(-1, self.cfg.hidden).index_select(0, positions)
         return self._mlm_logits(h)
 
+    def mlm_loss(self, ids, positions, labels, token_type=None, *,
+                 attention_mask=None, seq_lens=None, ignore_index=-100,
+                 reduction="mean"):
+        """The MLM loss at the masked positions (as forward_mlm; labels
+        int64 [len(positions)]) through ops.linear_cross_entropy on the
+        tied embedding weight and mlm_bias: on bf16 GPU tensors the
+        vocabulary projection and the cross-entropy are one kernel chain
+        and no logits are stored; elsewhere exactly
+        ``cross_entropy(forward_mlm(...).float(), labels)``."""
+        from sparkdl.ops import functional as F_
+        h = self.encode(ids, token_type, attention_mask=attention_mask,
+                        seq_lens=seq_lens)
+        h = h.reshape(-1, self.cfg.hidden).index_select(0, positions)
+        h = self.mlm_ln(torch.nn.functional.gelu(self.mlm_dense(h)))
+        return F_.linear_cross_entropy(
+            h, self.embeddings.word.weight.to(h.dtype), self.mlm_bias,
+            labels, ignore_index=ignore_index, reduction=reduction)
+
 
 def bert_pretrain_step(model, opt, batch, seq, device, use_cuda,
                        mask_frac=0.15, seq_lens=None):
@@ -249,9 +281,16 @@ def bert_pretrain_step(model, opt, batch, seq, device, use_cuda,
     # GEMM already sees bf16 operands and grads flow in bf16.
     pure_bf16 = model.embeddings.word.weight.dtype == torch.bfloat16
 
+    fused_mlm_loss = getattr(cfg, "fused_mlm_loss", False)
+
     def step():
         opt.zero_grad()
-        if pure_bf16:
+        if fused_mlm_loss:
+            with torch.autocast(autocast_dev, dtype=torch.bfloat16,
+                                enabled=not pure_bf16):
+                loss = model.mlm_loss(ids, positions, labels,
+                                      seq_lens=lens_dev)
+        elif pure_bf16:
             logits = model.forward_mlm(ids, positions,
                                        seq_lens=lens_dev)
             loss = torch.nn.functional.cross_entropy(

@@ -1,8 +1,9 @@
 """sparkdl.ops — hand-written CDNA4 (gfx950) kernels and their wrappers.
 
 Hot-path ops: fused multi-tensor AdamW/SGD,
-LayerNorm, dropout+add+LayerNorm, fused bias+GELU, and the 3x3 stride-1
-convolution (conv3x3 / Conv3x3, forward and dgrad).  The HIP extension (sparkdl._C) is built
+LayerNorm, dropout+add+LayerNorm, fused bias+GELU, the 3x3 stride-1
+convolution (conv3x3 / Conv3x3, forward and dgrad) and the fused
+vocabulary projection + cross-entropy (linear_cross_entropy).  The HIP extension (sparkdl._C) is built
 in-tree for gfx950; on a GPU these ops REQUIRE it — a missing extension
 raises instead of silently falling back to eager PyTorch.  On CPU
 tensors the pure-PyTorch reference path runs (that reference is also
@@ -45,6 +46,7 @@ from sparkdl.ops.functional import (  # noqa: F401,E402
     flash_attention, flash_attention_packed, masked_attention_ref,
     seqlens_from_mask, dropout_add_layer_norm, dropout_keep_mask,
     conv1x1_bn_act, conv3x3, conv3x3_route,
+    linear_cross_entropy, linear_cross_entropy_ok,
 )
 from sparkdl.ops.modules import (  # noqa: F401,E402
     LayerNorm, Linear, LinearGelu, Conv1x1, Conv3x3, BatchNormAct2d,

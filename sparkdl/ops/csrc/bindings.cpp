@@ -469,6 +469,117 @@ std::vector<at::Tensor> gemm_bias_act(const at::Tensor& A,
   return {C};
 }
 
+// ---------------------------------------------------------------------
+// Fused vocabulary projection + cross-entropy
+// ---------------------------------------------------------------------
+
+// Shared validation of h [M,K], weight [V,K], bias [V] and labels [M].
+static const float* lce_check(const char* op, const at::Tensor& h,
+                              const at::Tensor& weight,
+                              const c10::optional<at::Tensor>& bias,
+                              const at::Tensor& labels) {
+  CHECK_BF16_CUDA(h);
+  CHECK_BF16_CUDA(weight);
+  TORCH_CHECK(h.dim() == 2 && weight.dim() == 2 &&
+                  h.size(1) == weight.size(1),
+              op, " takes h [M,K] and weight [V,K], got ", h.sizes(), " and ",
+              weight.sizes());
+  TORCH_CHECK(lce_supported(h.size(0), weight.size(0), h.size(1)), op,
+              " requires K % 64 == 0, M >= 1 and 1 <= V <= 2^30, got h ",
+              h.sizes(), " weight ", weight.sizes());
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong &&
+                  labels.is_contiguous() && labels.dim() == 1 &&
+                  labels.size(0) == h.size(0),
+              op, ": labels must be contiguous int64 [M] on the GPU");
+  TORCH_CHECK(weight.device() == h.device() && labels.device() == h.device(),
+              op, ": tensors must share one device");
+  if (!bias.has_value()) return nullptr;
+  CHECK_F32_CUDA(bias.value());
+  TORCH_CHECK(bias->numel() == weight.size(0) &&
+                  bias->device() == h.device(),
+              op, ": bias must hold V fp32 values on h's device");
+  return bias->data_ptr<float>();
+}
+
+// -> {loss, lse [M], count int32 [1]}; loss is per row [M] for "none",
+// a 0-dim tensor for "sum" and "mean" (the sum over max(count, 1)).
+std::vector<at::Tensor> lce_forward(const at::Tensor& h,
+                                    const at::Tensor& weight,
+                                    const c10::optional<at::Tensor>& bias,
+                                    const at::Tensor& labels,
+                                    int64_t ignore_index,
+                                    const std::string& reduction) {
+  const float* bias_ptr = lce_check("lce_forward", h, weight, bias, labels);
+  TORCH_CHECK(reduction == "none" || reduction == "sum" ||
+                  reduction == "mean",
+              "lce_forward: reduction must be none, sum or mean, got ",
+              reduction);
+  DeviceGuard guard(h.device());
+  const int M = (int)h.size(0), K = (int)h.size(1), V = (int)weight.size(0);
+  auto f32 = h.options().dtype(at::kFloat);
+  auto ws = at::empty({(int64_t)lce_vtiles(V), M, 2}, f32);
+  auto zlab = at::empty({M}, f32);
+  auto loss = at::empty({M}, f32);
+  auto lse = at::empty({M}, f32);
+  auto count = at::empty({1}, h.options().dtype(at::kInt));
+  at::Tensor total;
+  if (reduction != "none") total = at::empty({}, f32);
+  launch_lce_forward(bf_ptr(h), bf_ptr(weight), bias_ptr,
+                     reinterpret_cast<const long long*>(
+                         labels.data_ptr<int64_t>()),
+                     reinterpret_cast<float2*>(ws.data_ptr<float>()),
+                     zlab.data_ptr<float>(), loss.data_ptr<float>(),
+                     lse.data_ptr<float>(), count.data_ptr<int>(),
+                     total.defined() ? total.data_ptr<float>() : nullptr,
+                     reduction == "mean", M, V, K, ignore_index,
+                     cur_stream());
+  return {total.defined() ? total : loss, lse, count};
+}
+
+// -> {dZ [M,V] bf16, a view of rows lce_ldz(V) elements apart whose
+// padding columns are zero; dbias [V] fp32}. gout: fp32, one value or
+// one per row; count (the forward's) divides it, for "mean".
+std::vector<at::Tensor> lce_backward(const at::Tensor& h,
+                                     const at::Tensor& weight,
+                                     const c10::optional<at::Tensor>& bias,
+                                     const at::Tensor& labels,
+                                     const at::Tensor& lse,
+                                     const at::Tensor& gout,
+                                     const c10::optional<at::Tensor>& count,
+                                     int64_t ignore_index) {
+  const float* bias_ptr = lce_check("lce_backward", h, weight, bias, labels);
+  CHECK_F32_CUDA(lse);
+  CHECK_F32_CUDA(gout);
+  const int M = (int)h.size(0), K = (int)h.size(1), V = (int)weight.size(0);
+  TORCH_CHECK(lse.numel() == M && lse.device() == h.device(),
+              "lce_backward: lse must hold M fp32 values on h's device");
+  TORCH_CHECK((gout.numel() == 1 || gout.numel() == M) &&
+                  gout.device() == h.device(),
+              "lce_backward: gout must hold 1 or M fp32 values on h's "
+              "device, got ", gout.numel());
+  const int* count_ptr = nullptr;
+  if (count.has_value()) {
+    TORCH_CHECK(count->is_cuda() && count->device() == h.device() &&
+                    count->scalar_type() == at::kInt && count->numel() == 1,
+                "lce_backward: count must be int32 [1] on h's device");
+    count_ptr = count->data_ptr<int>();
+  }
+  DeviceGuard guard(h.device());
+  const int64_t ldz = lce_ldz(V);
+  auto f32 = h.options().dtype(at::kFloat);
+  auto dz = at::empty({M, ldz}, h.options());
+  auto slab = at::empty({(int64_t)lce_bands(M), ldz}, f32);
+  auto dbias = at::empty({V}, f32);
+  launch_lce_backward(bf_ptr(h), bf_ptr(weight), bias_ptr,
+                      reinterpret_cast<const long long*>(
+                          labels.data_ptr<int64_t>()),
+                      lse.data_ptr<float>(), gout.data_ptr<float>(),
+                      gout.numel() == 1 ? 0 : 1, count_ptr, bf_ptr_mut(dz),
+                      slab.data_ptr<float>(), dbias.data_ptr<float>(), M, V,
+                      K, ignore_index, cur_stream());
+  return {dz.narrow(1, 0, V), dbias};
+}
+
 at::Tensor gemm_stream(const at::Tensor& A, const at::Tensor& W) {
   CHECK_BF16_CUDA(A);
   CHECK_BF16_CUDA(W);
@@ -916,6 +1027,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("zero_grads_", &zero_grads_, "Zero all grads in a chunk table");
   m.def("gemm_bias_act", &gemm_bias_act, "MFMA GEMM + bias(+GELU) (N6)");
   m.def("transpose_bf16", &transpose_bf16, "bf16 2D transpose (dgrad W^T)");
+  m.def("lce_forward", &lce_forward,
+        "Fused linear + cross-entropy forward -> loss, lse, count",
+        py::arg("h"), py::arg("weight"), py::arg("bias"), py::arg("labels"),
+        py::arg("ignore_index") = -100, py::arg("reduction") = "none");
+  m.def("lce_backward", &lce_backward,
+        "Fused linear + cross-entropy backward -> dZ (padded rows), dbias",
+        py::arg("h"), py::arg("weight"), py::arg("bias"), py::arg("labels"),
+        py::arg("lse"), py::arg("gout"), py::arg("count"),
+        py::arg("ignore_index") = -100);
   m.def("gemm_stream", &gemm_stream,
         "Streaming tall-skinny GEMM (1x1 convs)");
   m.def("conv1x1_stats", &conv1x1_stats,

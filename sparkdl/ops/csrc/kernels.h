@@ -168,6 +168,33 @@ void launch_gemm_bias_act(const short* A, const short* W,
                           int N, int K, int act, hipStream_t stream);
 bool gemm_bias_act_supported(int M, int N, int K);
 
+// Fused vocabulary projection + cross-entropy (csrc/linear_xent.hip):
+// z = h[M,K] @ W[V,K]^T + bias[V] (bf16 operands, fp32 z, bias nullable)
+// is never stored. Forward: loss[M] = lse - z[label] (0 where
+// labels[row] == ignore_index), lse[M], count[1] = rows that are not
+// ignored, and with total != nullptr total[1] = sum(loss), divided by
+// max(count, 1) if mean. ws (float2[lce_vtiles(V) * M]) and zlab
+// (float[M]) are uninitialized workspaces. Backward recomputes z and
+// writes dZ[M, lce_ldz(V)] bf16 (padding columns zero),
+// d = (softmax(z) - onehot(label)) * gout[row * gstride] / max(*count, 1)
+// (count nullable: no division), 0 on ignored rows, and dbias[V], the
+// fp32 column sums of d, through slab (float[lce_bands(M) * lce_ldz(V)],
+// uninitialized). gout, count and labels are read on the device only.
+bool lce_supported(long long M, long long V, long long K);
+int lce_bands(int M);
+int lce_vtiles(int V);
+int lce_ldz(int V);
+void launch_lce_forward(const short* h, const short* W, const float* bias,
+                        const long long* labels, float2* ws, float* zlab,
+                        float* loss, float* lse, int* count, float* total,
+                        bool mean, int M, int V, int K,
+                        long long ignore_index, hipStream_t stream);
+void launch_lce_backward(const short* h, const short* W, const float* bias,
+                         const long long* labels, const float* lse,
+                         const float* gout, int gstride, const int* count,
+                         short* dZ, float* slab, float* dbias, int M, int V,
+                         int K, long long ignore_index, hipStream_t stream);
+
 // Streaming tall-skinny GEMM (ResNet 1x1 convs): C = A @ W^T, W panel
 // resident in LDS, A fragments direct from global. K in {64,128,256},
 // N % 64 == 0.

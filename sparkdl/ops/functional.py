@@ -881,6 +881,90 @@ def conv3x3(x, weight):
     return torch.nn.functional.conv2d(x, weight, padding=1)
 
 
+# ---------------------------------------------------------------------------
+# Fused vocabulary projection + cross-entropy (csrc/linear_xent.hip)
+# ---------------------------------------------------------------------------
+
+class _LinearCrossEntropyFn(torch.autograd.Function):
+    """cross_entropy(h @ W^T + bias, labels) through lce_forward /
+    lce_backward. Saves the operands, lse [M] and the count of valid
+    rows; no [M, V] tensor outlives either pass but dZ, which lives
+    inside backward only. dh and dW are library GEMMs on dZ."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, labels, ignore_index, reduction):
+        C = _ops.ext()
+        loss, lse, count = C.lce_forward(h, weight, bias, labels,
+                                         ignore_index, reduction)
+        ctx.save_for_backward(h, weight, labels, lse, count,
+                              bias if bias is not None else torch.empty(0))
+        ctx.lce_args = (ignore_index, reduction, bias is not None)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        C = _ops.ext()
+        h, weight, labels, lse, count, bias = ctx.saved_tensors
+        ignore_index, reduction, has_bias = ctx.lce_args
+        dz, dbias = C.lce_backward(
+            h, weight, bias if has_bias else None, labels, lse,
+            gout.float().contiguous(),
+            count if reduction == "mean" else None, ignore_index)
+        dh = dz @ weight if ctx.needs_input_grad[0] else None
+        dw = dz.t() @ h if ctx.needs_input_grad[1] else None
+        db = dbias if has_bias and ctx.needs_input_grad[2] else None
+        return dh, dw, db, None, None, None
+
+
+def linear_cross_entropy_ok(h, weight, bias, labels):
+    """Inputs the fused kernels take: bf16 contiguous ``h [M, K]`` and
+    ``weight [V, K]`` on one GPU with ``K % 64 == 0``, an fp32 bias
+    ``[V]`` or none, int64 labels ``[M]``."""
+    if not (h.is_cuda and h.dtype == torch.bfloat16
+            and weight.dtype == torch.bfloat16
+            and weight.device == h.device
+            and h.dim() == 2 and weight.dim() == 2
+            and h.shape[0] >= 1 and weight.shape[0] >= 1
+            and h.shape[1] == weight.shape[1]
+            and h.shape[1] >= 64 and h.shape[1] % 64 == 0
+            and h.is_contiguous() and weight.is_contiguous()
+            and labels.device == h.device and labels.dtype == torch.int64
+            and labels.shape == (h.shape[0],) and labels.is_contiguous()):
+        return False
+    return bias is None or (
+        bias.device == h.device and bias.dtype == torch.float32
+        and bias.shape == (weight.shape[0],) and bias.is_contiguous())
+
+
+def linear_cross_entropy(h, weight, bias, labels, ignore_index=-100,
+                         reduction="mean"):
+    """``cross_entropy(h @ weight^T + bias, labels)``, fp32, for the
+    reductions ``"mean"``, ``"sum"`` and ``"none"``.
+
+    Inputs that pass ``linear_cross_entropy_ok`` run the fused kernels:
+    the logits are formed in fp32 tile by tile and reduced at once,
+    forward and (recomputed) backward, so no ``[M, V]`` tensor is kept
+    and the loss sees unrounded logits. Everything is bitwise
+    reproducible, nothing synchronises with the host. Labels outside
+    ``[0, V)`` other than ``ignore_index`` give NaN.
+
+    Everything else, all CPU inputs included, runs the composed ops,
+    whose logits are rounded to ``h``'s dtype: ``F.linear``, ``+
+    bias.to(dtype)``, ``.float()``, ``F.cross_entropy``."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError("reduction must be 'mean', 'sum' or 'none', got %r"
+                         % (reduction,))
+    if linear_cross_entropy_ok(h, weight, bias, labels):
+        return _LinearCrossEntropyFn.apply(h, weight, bias, labels,
+                                           int(ignore_index), reduction)
+    logits = torch.nn.functional.linear(h, weight)
+    if bias is not None:
+        logits = logits + bias.to(logits.dtype)
+    return torch.nn.functional.cross_entropy(
+        logits.float(), labels, ignore_index=ignore_index,
+        reduction=reduction)
+
+
 class _LinearFusedFn(torch.autograd.Function):
     """y = x @ W^T + b with the bias fused into the MFMA GEMM epilogue
     (act=0). dgrad runs on the same kernel via W^T; wgrad/dbias on
