@@ -1,8 +1,8 @@
 """Per-site A/B of the hand-written 3x3 convolution (csrc/conv3x3.hip)
 against MIOpen at the four stride-1 3x3 sites of ResNet-50, batch 512,
-bf16 channels_last: forward and data gradient, same tensors, same
-process. The two paths alternate window by window; each window is
-``--reps`` calls between two device events, after warm-up. Prints, per
+bf16 channels_last: forward, data gradient and weight gradient
+(``--passes``), same tensors, same process. The two paths alternate
+window by window; each window is ``--reps`` calls between two device events, after warm-up. Prints, per
 site and pass, the median microseconds per call of both paths, the
 TFLOP/s those give for the 2*N*H*W*9*Cin*Cout operations of the
 convolution, and MIOpen's time over the kernel's (> 1: the kernel is
@@ -45,6 +45,7 @@ def main():
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--passes", default="fwd,dgrad,wgrad")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("conv3x3_bench: no GPU")
@@ -79,19 +80,24 @@ def main():
             return conv_bwd(dy, x, w, None, [1, 1], [1, 1], [1, 1], False,
                             [0, 0], 1, [True, False, False])[0]
 
+        def wgrad_lib():
+            return conv_bwd(dy, x, w, None, [1, 1], [1, 1], [1, 1], False,
+                            [0, 0], 1, [False, True, False])[1]
+
+        passes = [p for p in (
+            ("fwd", lambda: C.conv3x3(xp, wf), fwd_lib),
+            ("dgrad", lambda: C.conv3x3(dyp, wb), dgrad_lib),
+            ("wgrad", lambda: C.conv3x3_wgrad(xp, dyp), wgrad_lib))
+            if p[0] in args.passes.split(",")]
         # same results first: fp32 accumulation on both sides, so the
         # difference is summation order and one bf16 rounding
-        for name, got, ref in (
-                ("fwd", C.conv3x3(xp, wf), fwd_lib().permute(0, 2, 3, 1)),
-                ("dgrad", C.conv3x3(dyp, wb),
-                 dgrad_lib().permute(0, 2, 3, 1))):
+        for name, ours, theirs in passes:
+            got, ref = ours(), theirs().permute(0, 2, 3, 1)
             err = (got.float() - ref.float()).abs().max().item()
             scale = ref.float().abs().max().item()
             assert err <= 2.0 ** -6 * scale, (hw, c, name, err, scale)
         flop = 2.0 * n * hw * hw * 9 * c * c
-        for name, ours, theirs in (
-                ("fwd", lambda: C.conv3x3(xp, wf), fwd_lib),
-                ("dgrad", lambda: C.conv3x3(dyp, wb), dgrad_lib)):
+        for name, ours, theirs in passes:
             t, m = ab(ours, theirs, args.reps, args.windows)
             print("%2dx%-2d C=%3d %-5s  conv3x3 %8.1f us %6.1f TF   "
                   "miopen %8.1f us %6.1f TF   miopen/conv3x3 %.2f"

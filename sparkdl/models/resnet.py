@@ -17,7 +17,8 @@ in-house 1x1 package (sparkdl.ops.Conv1x1 with SPARKDL_CONV1X1=1/all)
 stays opt-in, and so does the hand-written 3x3 kernel: each
 bottleneck's conv2 is a sparkdl.ops.Conv3x3, an nn.Conv2d that with
 SPARKDL_CONV3X3=1 runs forward and dgrad of its 13 stride-1 instances on
-csrc/conv3x3.hip (wgrad on MIOpen) and unset is MIOpen as before. Every
+csrc/conv3x3.hip (wgrad on MIOpen), with SPARKDL_CONV3X3=all their wgrad
+too (conv3x3_wgrad_k, deterministic), and unset is MIOpen as before. Every
 BatchNorm/ReLU/residual-add runs through sparkdl.ops' fused bf16-NHWC
 BatchNormAct2d kernels (SURVEY.md §2.2 N4/N5 — the conv-block epilogue
 fusion); the stem's BatchNorm + ReLU + 3x3/2 max-pool is one kernel chain

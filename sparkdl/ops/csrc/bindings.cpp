@@ -685,6 +685,54 @@ std::vector<int64_t> conv3x3_plan_py(int64_t n, int64_t h, int64_t w,
   return {rows, imgs, tiles, workers};
 }
 
+// dw [Cout,3,3,Cin] = weight gradient of conv3x3 from x [N,H,W,Cin] and
+// dy [N,H,W,Cout]. The per-worker fp32 slabs come from the caching
+// allocator and are fully written by the launch: no memset, no host
+// synchronisation, capturable.
+at::Tensor conv3x3_wgrad(const at::Tensor& x, const at::Tensor& dy,
+                         int64_t max_workers) {
+  CHECK_BF16_CUDA(x);
+  CHECK_BF16_CUDA(dy);
+  TORCH_CHECK(dy.device() == x.device(),
+              "conv3x3_wgrad: x and dy must share one device");
+  TORCH_CHECK(x.dim() == 4 && dy.dim() == 4,
+              "conv3x3_wgrad takes x as [N,H,W,Cin] and dy as [N,H,W,Cout]");
+  TORCH_CHECK(dy.size(0) == x.size(0) && dy.size(1) == x.size(1) &&
+                  dy.size(2) == x.size(2),
+              "conv3x3_wgrad: x ", x.sizes(), " and dy ", dy.sizes(),
+              " must agree in N, H and W");
+  const int64_t n = x.size(0), h = x.size(1), w = x.size(2);
+  const int64_t cin = x.size(3), cout = dy.size(3);
+  TORCH_CHECK(cin < (1 << 20) && cout < (1 << 20) &&
+                  conv3x3_supported(n, h, w, (int)cin, (int)cout),
+              "conv3x3_wgrad requires Cin and Cout multiples of 64,"
+              " 1 <= W <= 56, H >= 1 and N*H*W < 2^31, got x ", x.sizes(),
+              " dy ", dy.sizes());
+  TORCH_CHECK(max_workers >= 0 && max_workers < (1 << 20));
+  DeviceGuard guard(x.device());
+  int rows, imgs, tiles, workers;
+  conv3x3_wgrad_plan((int)n, (int)h, (int)w, (int)cin, (int)cout,
+                     (int)max_workers, &rows, &imgs, &tiles, &workers);
+  auto slabs = at::empty({workers, cout * 9 * cin},
+                         x.options().dtype(at::kFloat));
+  auto dw = at::empty({cout, 3, 3, cin}, x.options());
+  launch_conv3x3_wgrad(bf_ptr(x), bf_ptr(dy), slabs.data_ptr<float>(),
+                       bf_ptr_mut(dw), (int)n, (int)h, (int)w, (int)cin,
+                       (int)cout, (int)max_workers, cur_stream());
+  return dw;
+}
+
+std::vector<int64_t> conv3x3_wgrad_plan_py(int64_t n, int64_t h, int64_t w,
+                                           int64_t cin, int64_t cout,
+                                           int64_t max_workers) {
+  TORCH_CHECK(cin < (1 << 20) && cout < (1 << 20) &&
+              conv3x3_supported(n, h, w, (int)cin, (int)cout));
+  int rows, imgs, tiles, workers;
+  conv3x3_wgrad_plan((int)n, (int)h, (int)w, (int)cin, (int)cout,
+                     (int)max_workers, &rows, &imgs, &tiles, &workers);
+  return {rows, imgs, tiles, workers};
+}
+
 // ---------------------------------------------------------------------
 // Flash attention (D=64)
 // ---------------------------------------------------------------------
@@ -1052,6 +1100,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3_plan", &conv3x3_plan_py,
         "(rows per band, images per tile, tiles and workers per N-block) "
         "of a conv3x3 launch",
+        py::arg("n"), py::arg("h"), py::arg("w"), py::arg("cin"),
+        py::arg("cout"), py::arg("max_workers") = 0);
+  m.def("conv3x3_wgrad", &conv3x3_wgrad,
+        "Weight gradient [Cout,3,3,Cin] of the 3x3 stride-1 pad-1 "
+        "convolution, NHWC bf16, deterministic",
+        py::arg("x"), py::arg("dy"), py::arg("max_workers") = 0);
+  m.def("conv3x3_wgrad_plan", &conv3x3_wgrad_plan_py,
+        "(rows per band, images per tile, tiles and workers per block "
+        "pair) of a conv3x3_wgrad launch",
         py::arg("n"), py::arg("h"), py::arg("w"), py::arg("cin"),
         py::arg("cout"), py::arg("max_workers") = 0);
   m.def("bn_fwd_slab", &bn_fwd_slab,

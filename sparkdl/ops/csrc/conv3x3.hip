@@ -7,7 +7,8 @@
 // [Cout,Cin,3,3] weight), y [N,H,W,Cout]; fp32 accumulation, zero padding,
 // no bias, f2bf store. M = N*H*W, N = Cout, K = 9*Cin. The data gradient
 // is the same kernel on dy with the taps flipped and the channel roles
-// swapped, so this file serves forward and dgrad.
+// swapped, so conv3x3_k serves forward and dgrad. The weight gradient
+// (conv3x3_wgrad_k, further down) runs on the same tiles and halo staging.
 //
 // gemm_stream_k's "A fragments straight from global" would fetch every
 // input pixel nine times. Here the nine taps share one staged input halo:
@@ -109,6 +110,66 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// XOR applied to the 16 B chunk index of halo pixel p. conv3x3_k reads 16 B
+// per lane and 16 pixels per read: all three bits. conv3x3_wgrad_k reads
+// 8 B per lane and 4 pixels x 32 B per 16-lane group: the 32 B pair index.
+struct SwzPix8 {
+  static __device__ __forceinline__ int of(int p) { return p & 7; }
+};
+struct SwzPix4Pair {
+  static __device__ __forceinline__ int of(int p) { return (p & 3) << 1; }
+};
+
+// The two pad columns of every halo row: zero for the whole launch.
+__device__ __forceinline__ void zero_halo_pads(short* lH, int hrows, int W2,
+                                               int tid) {
+  const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int q = tid; q < hrows * 16; q += VTHREADS) {
+    const int pix = (q >> 4) * W2 + ((q & 8) ? W2 - 1 : 0);
+    *(bf16x8*)(lH + pix * VBK + (q & 7) * 8) = zero8;
+  }
+}
+
+// Halo slice ci0 .. ci0+63 of the tile at (img0, h0): the waves take halo
+// rows in turn. A row inside the image is loaded (its W pixels; the pads
+// stay zero), a row outside is zeroed if `first` and left alone otherwise.
+template <class Swz>
+__device__ __forceinline__ void stage_halo(short* lH,
+                                           const short* __restrict__ x,
+                                           const Geom& g, int img0, int h0,
+                                           int ci0, bool first, int wave,
+                                           int lane) {
+  const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  const int W2 = g.w + 2;
+  const int hrows_seg = g.rows + 2;
+  const int hrows = g.imgs * hrows_seg;
+  const int row_chunks = g.w * 8;  // 16 B chunks inside a halo row
+  int seg = 0, hr = wave;          // hrow = seg * hrows_seg + hr
+  for (int hrow = wave; hrow < hrows; hrow += VWAVES, hr += VWAVES) {
+    while (hr >= hrows_seg) {
+      hr -= hrows_seg;
+      ++seg;
+    }
+    const int img = img0 + seg, ih = h0 + hr - 1;
+    if (img >= g.n) break;  // the tile has fewer images
+    const int pix0 = hrow * W2 + 1;
+    if (ih >= 0 && ih < g.h) {
+      const short* src =
+          x + (((long long)img * g.h + ih) * g.w) * g.cin + ci0;
+      for (int j0 = 0; j0 < row_chunks; j0 += 64) {
+        const bool on = j0 + lane < row_chunks;
+        const int j = on ? j0 + lane : 0;  // a valid address in any lane
+        const int kc = (j & 7) ^ Swz::of(pix0 + (j >> 3));
+        const short* gp = src + (long long)(j >> 3) * g.cin + kc * 8;
+        if (on) global_load_lds16(gp, lH + (pix0 * 8 + j0) * 8);
+      }
+    } else if (first) {
+      for (int j = lane; j < row_chunks; j += 64)
+        *(bf16x8*)(lH + (pix0 * 8 + j) * 8) = zero8;
+    }
+  }
+}
+
 __global__ __launch_bounds__(VTHREADS) void conv3x3_k(
     const short* __restrict__ x, const short* __restrict__ wt,
     short* __restrict__ y, const Geom g) {
@@ -136,11 +197,7 @@ __global__ __launch_bounds__(VTHREADS) void conv3x3_k(
   const int hrows = g.imgs * hrows_seg;
   const int row_chunks = g.w * 8;      // 16 B chunks inside a halo row
 
-  // the two pad columns of every halo row: zero for the whole launch
-  for (int q = tid; q < hrows * 16; q += VTHREADS) {
-    const int pix = (q >> 4) * W2 + ((q & 8) ? W2 - 1 : 0);
-    *(bf16x8*)(lH + pix * VBK + (q & 7) * 8) = zero8;
-  }
+  zero_halo_pads(lH, hrows, W2, tid);
 
   // halo index of the lane's output pixel in each of the 4 M fragments
   int hb[4];
@@ -173,36 +230,6 @@ __global__ __launch_bounds__(VTHREADS) void conv3x3_k(
     }
   };
 
-  // halo slice: the waves take halo rows in turn. A row inside the image
-  // is loaded (its W pixels; the pads stay zero), a row outside is zeroed
-  // on the tile's first slice and left alone afterwards.
-  auto stage_halo = [&](int img0, int h0, int ci0, bool first) {
-    int seg = 0, hr = wave;  // hrow = seg * hrows_seg + hr
-    for (int hrow = wave; hrow < hrows; hrow += VWAVES, hr += VWAVES) {
-      while (hr >= hrows_seg) {
-        hr -= hrows_seg;
-        ++seg;
-      }
-      const int img = img0 + seg, ih = h0 + hr - 1;
-      if (img >= g.n) break;  // the tile has fewer images
-      const int pix0 = hrow * W2 + 1;
-      if (ih >= 0 && ih < g.h) {
-        const short* src =
-            x + (((long long)img * g.h + ih) * g.w) * g.cin + ci0;
-        for (int j0 = 0; j0 < row_chunks; j0 += 64) {
-          const bool on = j0 + lane < row_chunks;
-          const int j = on ? j0 + lane : 0;  // a valid address in any lane
-          const int kc = (j & 7) ^ ((pix0 + (j >> 3)) & 7);
-          const short* gp = src + (long long)(j >> 3) * g.cin + kc * 8;
-          if (on) global_load_lds16(gp, lH + (pix0 * 8 + j0) * 8);
-        }
-      } else if (first) {
-        for (int j = lane; j < row_chunks; j += 64)
-          *(bf16x8*)(lH + (pix0 * 8 + j) * 8) = zero8;
-      }
-    }
-  };
-
   const int nslices = g.cin / VBK;
   if (nslices == 1) stage_w(0);  // the whole panel: resident
 
@@ -220,7 +247,7 @@ __global__ __launch_bounds__(VTHREADS) void conv3x3_k(
 
     for (int s = 0; s < nslices; ++s) {
       __syncthreads();  // the previous slice's fragment reads are done
-      stage_halo(img0, h0, s * VBK, s == 0);
+      stage_halo<SwzPix8>(lH, x, g, img0, h0, s * VBK, s == 0, wave, lane);
       if (nslices > 1) stage_w(s * VBK);
       __builtin_amdgcn_s_waitcnt(0);
       __syncthreads();
@@ -284,6 +311,234 @@ __global__ __launch_bounds__(VTHREADS) void conv3x3_k(
   }
 }
 
+// ---------------------------------------------------------------------
+// Weight gradient (conv3x3_wgrad_k + conv3x3_wgrad_reduce_k)
+//
+//   dw[co,kh,kw,ci] = sum_{n,h,w} dy[n,h,w,co] * x[n,h+kh-1,w+kw-1,ci]
+//
+// Per tap a GEMM with M = co, N = ci and the contraction over pixels, on
+// the tiles of the forward: the staged halo serves all nine taps.
+//
+// Work split
+//   - one workgroup per (64-co block, 64-ci block) pair and worker; it
+//     owns all nine taps of the pair: 9 x 64 x 64 fp32 accumulators that
+//     stay in registers over all of the worker's tiles w, w + workers, ...;
+//   - 4 waves; wave v owns all 64 co, the 16-ci fragment v and the 9 taps:
+//     4 x 9 = 36 accumulator fragments. A 32-pixel K-step reads 4 dy
+//     fragments and 9 x fragments (26 b64 transpose reads) for 36 MFMAs;
+//     16 co x 64 ci per wave would read 74, 32 x 32 would read 40;
+//   - each worker stores its accumulators once, fp32, into its own slab
+//     [worker][Cout,3,3,Cin]; conv3x3_wgrad_reduce_k adds the slabs in a
+//     fixed order and stores bf16. No atomics, no memset: every slab
+//     entry is written, and the result does not depend on timing.
+//
+// Operands are pixel-major in LDS (as in memory), MFMA wants them
+// contraction-major: ds_read_b64_tr_b16 transposes on the read. A 16-lane
+// group reads 4 pixels x 16 channels; lane l names pixel l/4, channels
+// 4*(l%4) .. +4 and receives channel l%16 of the 4 pixels. Two reads
+// (pixels 8g .. 8g+3 and 8g+4 .. 8g+7 of the K-step for group g) make one
+// operand fragment. Every lane supplies its own address, so the pixel of
+// a lane may lie anywhere: for x it is slot -> halo index (table lT, built
+// once per launch) + kh*(W+2) + kw, the forward's one add per tap.
+//
+// LDS map (dynamic, 85 KiB; one workgroup per CU):
+//   [0, 53248)       halo, 416 pixels x 128 B, staged as in the forward
+//                    but with the chunk XOR of SwzPix4Pair
+//   [53248, 86016)   dy, 256 pixel slots x 128 B (64 co), a linear copy:
+//                    the tile's pixels are contiguous in dy; same XOR
+//   [86016, 87040)   lT: halo index of each pixel slot (int)
+// Single-buffered: barrier, stage, barrier, up to 8 K-steps of 36 MFMAs.
+//
+// Slots that are no pixel (short band, fewer images, slots past rows*W,
+// tail of the last K-step) contribute exactly zero whatever LDS held:
+// their dy slots are zeroed with plain stores up to the end of the last
+// K-step that holds a pixel (later K-steps are skipped) and are never a
+// load target, and their x reads go to halo pixel 0, a pad slot that is
+// zero for the whole launch, so no stale Inf or NaN meets the zero.
+//
+// Bank conflicts: a 16-lane group reads 4 pixels x 32 B. Rows are 128 B,
+// so unswizzled the four would share 32 B of the 128-byte period. XOR of
+// the 32 B pair index with p & 3 puts 4 consecutive pixels on the four
+// pairs: conflict-free for dy (groups start at multiples of 4) and for x
+// wherever the 4 halo pixels are consecutive; a group that wraps to the
+// next halo row (+2) can repeat one value (2-way). That is per 16-lane
+// group only; the counters say the whole picture is worse: bank-conflict
+// cycles are 45-54 % of the LDS-active cycles at the four ResNet-50 sites
+// (profiles/README.md), so the groups of a wave, or the waves, collide.
+//
+// Registers: 144 accumulator + 16 dy + 36 x operand registers, 2 halo
+// indices, 4 dy offsets; launch_bounds(256) allows 512. Measured use,
+// scratch (0) and occupancy: profiles/README.md.
+// ---------------------------------------------------------------------
+
+constexpr int kDyElems = VMT * VBN;
+constexpr int kWgLds = (kHaloElems + kDyElems) * 2 + VMT * 4;
+static_assert(kWgLds <= 160 * 1024, "one workgroup fits a CU's LDS");
+
+typedef __attribute__((address_space(3))) short4v* lds_b64_ptr;
+
+// One hardware transpose read at LDS byte address a (see above).
+__device__ __forceinline__ short4v lds_tr_b64(unsigned a) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b64_ptr)a);
+}
+// The operand fragment made of the reads at a0 and a1.
+__device__ __forceinline__ bf16x8 tr_frag2(unsigned a0, unsigned a1) {
+  const short4v v0 = lds_tr_b64(a0), v1 = lds_tr_b64(a1);
+  return bf16x8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+}
+
+__global__ __launch_bounds__(VTHREADS) void conv3x3_wgrad_k(
+    const short* __restrict__ x, const short* __restrict__ dy,
+    float* __restrict__ slabs, const Geom g) {
+  extern __shared__ __attribute__((aligned(16))) short lds[];
+  short* lH = lds;
+  short* lD = lds + kHaloElems;
+  int* lT = (int*)(lD + kDyElems);
+
+  const int ncib = g.cin / VBK;
+  const int npairs = (g.cout / VBN) * ncib;
+  const int pair = blockIdx.x % npairs;
+  const int widx = blockIdx.x / npairs;  // worker of the pair
+  const int nworkers = gridDim.x / npairs;
+  const int cob = pair / ncib, cib = pair - cob * ncib;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const FragLane fl(lane);
+  const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+
+  const int W2 = g.w + 2;
+  const int seg_px = g.rows * g.w;
+  const int seg_hp = (g.rows + 2) * W2;
+  const int tile_px = g.imgs * seg_px;
+
+  zero_halo_pads(lH, g.imgs * (g.rows + 2), W2, tid);
+  // halo index of every pixel slot; slots past the tile are never valid
+  for (int p = tid; p < VMT; p += VTHREADS) {
+    int hb = 0;
+    if (p < tile_px) {
+      const int seg = p / seg_px;
+      const int r = (p - seg * seg_px) / g.w;
+      hb = seg * seg_hp + r * W2 + (p - seg * seg_px - r * g.w);
+    }
+    lT[p] = hb;
+  }
+
+  // the lane's part in a transpose read: pixel slot sl (+4 for the second
+  // read) of the K-step, 8 bytes at lgoff of the 32 B of its fragment
+  const int lg = lane & 15;
+  const int sl = (lane >> 4) * 8 + (lg >> 2);
+  const int lgoff = (lg & 3) * 8;
+  const unsigned hbase = (unsigned)(unsigned long long)(
+      (__attribute__((address_space(3))) short*)lH) + lgoff;
+  // dy fragment i: slot s & 3 == lg >> 2, so the pair index is i ^ (lg >> 2)
+  unsigned dbase[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    dbase[i] = (unsigned)(unsigned long long)(
+                   (__attribute__((address_space(3))) short*)lD) +
+               sl * 128 + ((i ^ (lg >> 2)) << 5) + lgoff;
+
+  f32x4 acc[4][9];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int t = 0; t < 9; ++t) acc[i][t] = {0.f, 0.f, 0.f, 0.f};
+
+  for (int tile = widx; tile < g.tiles; tile += nworkers) {
+    const int ti = tile / g.nbands;
+    const int img0 = ti * g.imgs;
+    const int h0 = (tile - ti * g.nbands) * g.rows;
+    // slot p < nvalid is pixel base_px + p of x and dy
+    const int vimgs = g.n - img0 < g.imgs ? g.n - img0 : g.imgs;
+    const int vrows = g.h - h0 < g.rows ? g.h - h0 : g.rows;
+    const int nvalid = (vimgs - 1) * seg_px + vrows * g.w;
+    const long long base_px = ((long long)img0 * g.h + h0) * g.w;
+    const int nk = (nvalid + 31) >> 5;  // K-steps that hold a pixel
+
+    __syncthreads();  // the previous tile's fragment reads are done
+    stage_halo<SwzPix4Pair>(lH, x, g, img0, h0, cib * VBK, true, wave, lane);
+    const short* src = dy + base_px * g.cout + cob * VBN;
+    const int nchunks = nvalid * 8;  // 16 B chunks that hold dy
+    for (int q0 = wave * 64; q0 < nchunks; q0 += VTHREADS) {
+      const bool on = q0 + lane < nchunks;
+      const int q = on ? q0 + lane : 0;  // a valid address in any lane
+      const int kc = (q & 7) ^ SwzPix4Pair::of(q >> 3);
+      const short* gp = src + (long long)(q >> 3) * g.cout + kc * 8;
+      if (on) global_load_lds16(gp, lD + q0 * 8);
+    }
+    for (int q = nchunks + tid; q < nk * 32 * 8; q += VTHREADS)
+      *(bf16x8*)(lD + q * 8) = zero8;
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+
+    for (int ks = 0; ks < nk; ++ks) {
+      const int s0 = ks * 32 + sl;
+      const int hb0 = lT[s0], hb1 = lT[s0 + 4];
+      const bool ok0 = s0 < nvalid, ok1 = s0 + 4 < nvalid;
+      bf16x8 a[4], b[9];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const unsigned d = dbase[i] + ks * (32 * 128);
+        a[i] = tr_frag2(d, d + 4 * 128);
+      }
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        const int toff = (t / 3) * W2 + t % 3;
+        const int p0 = ok0 ? hb0 + toff : 0, p1 = ok1 ? hb1 + toff : 0;
+        b[t] = tr_frag2(hbase + p0 * 128 + ((wave ^ (p0 & 3)) << 5),
+                        hbase + p1 * 128 + ((wave ^ (p1 & 3)) << 5));
+      }
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          acc[i][t] = mfma_bf16(a[i], b[t], acc[i][t]);
+      __builtin_amdgcn_s_setprio(0);
+    }
+  }
+
+  // C fragment (i, t): co = 16 i + c_sub_row + r, ci = 16 wave + c_col
+  float* slab = slabs + (long long)widx * g.cout * 9 * g.cin;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const long long co = cob * VBN + i * 16 + fl.c_sub_row + rr;
+      float* row = slab + co * 9 * g.cin + cib * VBK + wave * 16 + fl.c_col;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) row[t * g.cin] = acc[i][t][rr];
+    }
+}
+
+// dw = bf16(sum of the slabs). A block takes RQ float4 columns; thread
+// (q, part) adds the slabs part*per .. part*per+per-1 in order, then part 0
+// adds the RP partial sums in order: a fixed tree, 1/RP of the chain.
+constexpr int RQ = 32, RP = 8;
+static_assert(VBN * VBK * 9 / 4 % RQ == 0, "whole blocks of float4 columns");
+
+__global__ __launch_bounds__(RQ* RP) void conv3x3_wgrad_reduce_k(
+    const float4v* __restrict__ slabs, short4v* __restrict__ dw,
+    long long quads, int workers) {
+  __shared__ float4v part[RP][RQ];
+  const int qi = threadIdx.x % RQ, pt = threadIdx.x / RQ;
+  const long long q = (long long)blockIdx.x * RQ + qi;
+  const int per = (workers + RP - 1) / RP;
+  const int w1 = (pt + 1) * per < workers ? (pt + 1) * per : workers;
+  float4v s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+  for (int w = pt * per; w < w1; ++w) s += slabs[w * quads + q];
+  part[pt][qi] = s;
+  __syncthreads();
+  if (pt == 0) {
+#pragma unroll
+    for (int k = 1; k < RP; ++k) s += part[k][qi];
+    dw[q] = short4v{f2bf(s[0]), f2bf(s[1]), f2bf(s[2]), f2bf(s[3])};
+  }
+}
+
 int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // rows, imgs, nbands of the tiling described in the header
@@ -304,11 +559,12 @@ void tile_shape(int h, int w, int* rows, int* imgs, int* nbands) {
   *imgs = 1;
 }
 
-// rows, imgs, nbands and tiles of g, and the workers per N-block
-int plan(Geom* g, int max_workers) {
+// rows, imgs, nbands and tiles of g, and the workers per block of the
+// `blocks` output blocks that share the CUs
+int plan(Geom* g, int blocks, int max_workers) {
   tile_shape(g->h, g->w, &g->rows, &g->imgs, &g->nbands);
   g->tiles = g->nbands > 1 ? g->n * g->nbands : ceil_div(g->n, g->imgs);
-  int workers = kCUs / (g->cout / VBN);
+  int workers = kCUs / blocks;
   if (workers < 1) workers = 1;
   if (workers > g->tiles) workers = g->tiles;
   if (max_workers > 0 && workers > max_workers) workers = max_workers;
@@ -337,7 +593,7 @@ bool conv3x3_supported(long long n, long long h, long long w, int cin,
 void conv3x3_plan(int n, int h, int w, int cin, int cout, int max_workers,
                   int* rows, int* imgs, int* tiles, int* workers) {
   Geom g{n, h, w, cin, cout, 0, 0, 0, 0};
-  *workers = plan(&g, max_workers);
+  *workers = plan(&g, cout / VBN, max_workers);
   *rows = g.rows;
   *imgs = g.imgs;
   *tiles = g.tiles;
@@ -351,7 +607,38 @@ void launch_conv3x3(const short* x, const short* wt, short* y, int n, int h,
       kLds);
   (void)lds_set;
   Geom g{n, h, w, cin, cout, 0, 0, 0, 0};
-  const int workers = plan(&g, max_workers);
+  const int workers = plan(&g, cout / VBN, max_workers);
   hipLaunchKernelGGL(conv3x3_k, dim3((cout / VBN) * workers),
                      dim3(VTHREADS), kLds, stream, x, wt, y, g);
+}
+
+// Launch plan of the weight gradient: the forward's tile, tiles per
+// (co-block, ci-block) pair, and workers per pair: one workgroup per CU
+// over all pairs, at most one per tile; max_workers > 0 lowers it further.
+void conv3x3_wgrad_plan(int n, int h, int w, int cin, int cout,
+                        int max_workers, int* rows, int* imgs, int* tiles,
+                        int* workers) {
+  Geom g{n, h, w, cin, cout, 0, 0, 0, 0};
+  *workers = plan(&g, (cout / VBN) * (cin / VBK), max_workers);
+  *rows = g.rows;
+  *imgs = g.imgs;
+  *tiles = g.tiles;
+}
+
+void launch_conv3x3_wgrad(const short* x, const short* dy, float* slabs,
+                          short* dw, int n, int h, int w, int cin, int cout,
+                          int max_workers, hipStream_t stream) {
+  static const hipError_t lds_set = hipFuncSetAttribute(
+      (const void*)&conv3x3_wgrad_k,
+      hipFuncAttributeMaxDynamicSharedMemorySize, kWgLds);
+  (void)lds_set;
+  Geom g{n, h, w, cin, cout, 0, 0, 0, 0};
+  const int pairs = (cout / VBN) * (cin / VBK);
+  const int workers = plan(&g, pairs, max_workers);
+  hipLaunchKernelGGL(conv3x3_wgrad_k, dim3(pairs * workers), dim3(VTHREADS),
+                     kWgLds, stream, x, dy, slabs, g);
+  const long long quads = (long long)cout * 9 * cin / 4;
+  hipLaunchKernelGGL(conv3x3_wgrad_reduce_k, dim3((unsigned)(quads / RQ)),
+                     dim3(RQ * RP), 0, stream, (const float4v*)slabs,
+                     (short4v*)dw, quads, workers);
 }

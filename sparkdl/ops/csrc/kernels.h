@@ -231,6 +231,21 @@ void launch_conv3x3(const short* x, const short* wt, short* y, int n, int h,
                     int w, int cin, int cout, int max_workers,
                     hipStream_t stream);
 
+// Weight gradient of that convolution (csrc/conv3x3.hip):
+// dw[co,kh,kw,ci] = sum dy[n,h,w,co] * x[n,h+kh-1,w+kw-1,ci], x [n,h,w,cin],
+// dy [n,h,w,cout], dw [cout,3,3,cin] bf16 (f2bf of the fp32 sum). Same
+// shapes and tiles as the forward. conv3x3_wgrad_plan gives rows, imgs,
+// the tiles per (64-co, 64-ci) block pair and the persistent workers per
+// pair. `slabs` is fp32 scratch [workers][cout*9*cin], every entry of
+// which the launch writes before it reads it: no atomics, no memset, the
+// same bits on every run.
+void conv3x3_wgrad_plan(int n, int h, int w, int cin, int cout,
+                        int max_workers, int* rows, int* imgs, int* tiles,
+                        int* workers);
+void launch_conv3x3_wgrad(const short* x, const short* dy, float* slabs,
+                          short* dw, int n, int h, int w, int cin, int cout,
+                          int max_workers, hipStream_t stream);
+
 // Split-M wgrad GEMM (dW = dZ^T @ X, M-major operands): blocked-LDS
 // tr_b16 fragment path, fp32 output with split atomics. Ships behind
 // SPARKDL_FUSED_WGRAD=1 (Tensile still measures faster).

@@ -829,17 +829,28 @@ def conv3x3_route(cin, cout, stride=1, mode=None):
             and conv3x3_supported(1, 1, 1, cin, cout))
 
 
+def conv3x3_wgrad_route(mode=None):
+    """Whether a routed ``conv3x3`` also computes its weight gradient
+    in-house (conv3x3_wgrad_k). ``mode`` defaults to SPARKDL_CONV3X3:
+    only "all" says yes; "1" keeps the library's weight gradient."""
+    if mode is None:
+        mode = os.environ.get("SPARKDL_CONV3X3", "0")
+    return mode == "all"
+
+
 class _Conv3x3Fn(torch.autograd.Function):
     """y = conv2d(x, weight, padding=1) on channels_last bf16 tensors.
     Forward and dgrad run the conv3x3 kernel, dgrad on dy with the taps
-    flipped and the channel roles swapped; wgrad is the library's.
+    flipped and the channel roles swapped; wgrad is conv3x3_wgrad_k if
+    ``wgrad`` and the library's otherwise.
     channels_last [N,C,H,W] is [N,H,W,C] as a view, and a channels_last
     weight [Cout,Cin,3,3] is the kernel's [Cout,3,3,Cin] as a view."""
 
     @staticmethod
-    def forward(ctx, x, weight):
+    def forward(ctx, x, weight, wgrad):
         C = _ops.ext()
         ctx.save_for_backward(x, weight)
+        ctx.wgrad = wgrad
         y = C.conv3x3(x.permute(0, 2, 3, 1),
                       weight.permute(0, 2, 3, 1).contiguous(), 0)
         return y.permute(0, 3, 1, 2)
@@ -854,21 +865,27 @@ class _Conv3x3Fn(torch.autograd.Function):
             # [Cout,Cin,kh,kw] -> [Cin, 2-kh, 2-kw, Cout]
             wt = weight.flip(2, 3).permute(1, 2, 3, 0).contiguous()
             dx = C.conv3x3(dy.permute(0, 2, 3, 1), wt, 0).permute(0, 3, 1, 2)
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and ctx.wgrad:
+            # [Cout,3,3,Cin] is a channels_last [Cout,Cin,3,3] as a view
+            dw = C.conv3x3_wgrad(x.permute(0, 2, 3, 1),
+                                 dy.permute(0, 2, 3, 1), 0).permute(0, 3, 1, 2)
+        elif ctx.needs_input_grad[1]:
             dw = torch.ops.aten.convolution_backward(
                 dy, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0],
                 1, [False, True, False])[1]
-        return dx, dw
+        return dx, dw, None
 
 
-def conv3x3(x, weight):
+def conv3x3(x, weight, wgrad=None):
     """``conv2d(x, weight, padding=1)`` for a 3x3 ``weight``
     [Cout,Cin,3,3] and ``x`` [N,Cin,H,W].
 
     bf16 channels_last GPU tensors of a supported shape (Cin and Cout
     multiples of 64, W <= 56, N*H*W < 2^31) run the hand-written
-    implicit-GEMM kernel forward and for the data gradient; the weight
-    gradient is the library's. Everything else is
+    implicit-GEMM kernel forward and for the data gradient. The weight
+    gradient is the hand-written, deterministic conv3x3_wgrad_k with
+    ``wgrad=True`` and the library's with ``wgrad=False``; ``None`` asks
+    ``conv3x3_wgrad_route()`` (SPARKDL_CONV3X3=all). Everything else is
     ``torch.nn.functional.conv2d(x, weight, padding=1)`` exactly."""
     if (x.is_cuda and weight.is_cuda and x.dim() == 4 and weight.dim() == 4
             and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
@@ -877,7 +894,9 @@ def conv3x3(x, weight):
             and x.is_contiguous(memory_format=torch.channels_last)
             and conv3x3_supported(x.shape[0], x.shape[2], x.shape[3],
                                   x.shape[1], weight.shape[0])):
-        return _Conv3x3Fn.apply(x, weight)
+        if wgrad is None:
+            wgrad = conv3x3_wgrad_route()
+        return _Conv3x3Fn.apply(x, weight, bool(wgrad))
     return torch.nn.functional.conv2d(x, weight, padding=1)
 
 

@@ -223,9 +223,14 @@ class Conv3x3(nn.Conv2d):
     counts that are multiples of 64 (13 of ResNet-50's 16) to the
     hand-written implicit-GEMM kernel of csrc/conv3x3.hip for forward
     and dgrad, on bf16 channels_last GPU inputs; wgrad stays on the
-    library. Opt-in: scripts/conv3x3_bench.py times the kernel against
-    MIOpen at the four ResNet-50 sites (profiles/conv3x3_sites.log;
-    profiles/README.md, "3x3 convolution kernel")."""
+    library. ``SPARKDL_CONV3X3=all`` moves the weight gradient of those
+    instances too, to conv3x3_wgrad_k of the same file: per-worker fp32
+    slabs summed in a fixed order, no float atomics, the same bits on
+    every run (``functional.conv3x3_wgrad_route``). Opt-in:
+    scripts/conv3x3_bench.py times the kernels against MIOpen at the
+    four ResNet-50 sites (profiles/conv3x3_sites.log,
+    profiles/conv3x3_wgrad_sites.log; profiles/README.md, "3x3
+    convolution kernel" and "3x3 convolution weight gradient")."""
 
     def __init__(self, cin, cout, stride=1):
         super().__init__(cin, cout, 3, stride=stride, padding=1, bias=False)
