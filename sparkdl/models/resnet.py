@@ -18,7 +18,10 @@ stays opt-in, and so does the hand-written 3x3 kernel: each
 bottleneck's conv2 is a sparkdl.ops.Conv3x3, an nn.Conv2d that with
 SPARKDL_CONV3X3=1 runs forward and dgrad of its 13 stride-1 instances on
 csrc/conv3x3.hip (wgrad on MIOpen), with SPARKDL_CONV3X3=all their wgrad
-too (conv3x3_wgrad_k, deterministic), and unset is MIOpen as before. Every
+too (conv3x3_wgrad_k, deterministic), and unset is MIOpen as before. The
+other 3 of the 16, the stride-2 conv2 that opens stages 2, 3 and 4, have a
+switch of their own: SPARKDL_CONV3X3_S2=1 runs their forward and dgrad on
+csrc/conv3x3_s2.hip (wgrad on MIOpen); unset is MIOpen as before. Every
 BatchNorm/ReLU/residual-add runs through sparkdl.ops' fused bf16-NHWC
 BatchNormAct2d kernels (SURVEY.md §2.2 N4/N5 — the conv-block epilogue
 fusion); the stem's BatchNorm + ReLU + 3x3/2 max-pool is one kernel chain

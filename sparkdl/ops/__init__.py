@@ -3,7 +3,8 @@
 Hot-path ops: fused multi-tensor AdamW/SGD,
 LayerNorm, dropout+add+LayerNorm, fused bias+GELU, the 3x3 stride-1
 convolution (conv3x3 / Conv3x3: forward, dgrad and, with
-SPARKDL_CONV3X3=all, the deterministic wgrad) and the fused
+SPARKDL_CONV3X3=all, the deterministic wgrad; at stride 2, forward and
+dgrad of csrc/conv3x3_s2.hip behind SPARKDL_CONV3X3_S2=1) and the fused
 vocabulary projection + cross-entropy (linear_cross_entropy).  The HIP extension (sparkdl._C) is built
 in-tree for gfx950; on a GPU these ops REQUIRE it — a missing extension
 raises instead of silently falling back to eager PyTorch.  On CPU
@@ -47,6 +48,7 @@ from sparkdl.ops.functional import (  # noqa: F401,E402
     flash_attention, flash_attention_packed, masked_attention_ref,
     seqlens_from_mask, dropout_add_layer_norm, dropout_keep_mask,
     conv1x1_bn_act, conv3x3, conv3x3_route, conv3x3_wgrad_route,
+    conv3x3_s2_route, conv3x3_s2_supported,
     linear_cross_entropy, linear_cross_entropy_ok,
 )
 from sparkdl.ops.modules import (  # noqa: F401,E402

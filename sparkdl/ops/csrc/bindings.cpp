@@ -734,6 +734,97 @@ std::vector<int64_t> conv3x3_wgrad_plan_py(int64_t n, int64_t h, int64_t w,
 }
 
 // ---------------------------------------------------------------------
+// 3x3 stride-2 pad-1 convolution, NHWC bf16
+// ---------------------------------------------------------------------
+
+// y [N,Ho,Wo,Cout] = conv3x3 at stride 2 of x [N,H,W,Cin] with
+// wt [Cout,3,3,Cin], zero padding, no bias.
+at::Tensor conv3x3_s2(const at::Tensor& x, const at::Tensor& wt,
+                      int64_t max_workers) {
+  CHECK_BF16_CUDA(x);
+  CHECK_BF16_CUDA(wt);
+  TORCH_CHECK(wt.device() == x.device(),
+              "conv3x3_s2: x and wt must share one device");
+  TORCH_CHECK(x.dim() == 4 && wt.dim() == 4,
+              "conv3x3_s2 takes x as [N,H,W,Cin] and wt as [Cout,3,3,Cin]");
+  TORCH_CHECK(wt.size(3) == x.size(3), "conv3x3_s2: x has ", x.size(3),
+              " input channels, wt has ", wt.size(3));
+  TORCH_CHECK(wt.size(1) == 3 && wt.size(2) == 3,
+              "conv3x3_s2 takes 3x3 taps, got ", wt.size(1), "x", wt.size(2));
+  const int64_t n = x.size(0), h = x.size(1), w = x.size(2);
+  const int64_t cin = x.size(3), cout = wt.size(0);
+  TORCH_CHECK(cin < (1 << 20) && cout < (1 << 20) &&
+                  conv3x3_s2_supported(n, h, w, (int)cin, (int)cout),
+              "conv3x3_s2 requires Cin and Cout multiples of 64,"
+              " 1 <= W <= 56, H >= 1 and N*H*W < 2^31, got x ", x.sizes(),
+              " wt ", wt.sizes());
+  TORCH_CHECK(max_workers >= 0 && max_workers < (1 << 20));
+  DeviceGuard guard(x.device());
+  auto y = at::empty({n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, cout},
+                     x.options());
+  launch_conv3x3_s2(bf_ptr(x), bf_ptr(wt), bf_ptr_mut(y), (int)n, (int)h,
+                    (int)w, (int)cin, (int)cout, (int)max_workers,
+                    cur_stream());
+  return y;
+}
+
+// dx [N,h,w,Cin] = data gradient of that convolution from
+// dy [N,Ho,Wo,Cout] and wd [Cin,3,3,Cout] (unflipped).
+at::Tensor conv3x3_s2_dgrad(const at::Tensor& dy, const at::Tensor& wd,
+                            int64_t h, int64_t w, int64_t max_workers) {
+  CHECK_BF16_CUDA(dy);
+  CHECK_BF16_CUDA(wd);
+  TORCH_CHECK(wd.device() == dy.device(),
+              "conv3x3_s2_dgrad: dy and wd must share one device");
+  TORCH_CHECK(dy.dim() == 4 && wd.dim() == 4,
+              "conv3x3_s2_dgrad takes dy as [N,Ho,Wo,Cout] and wd as "
+              "[Cin,3,3,Cout]");
+  TORCH_CHECK(wd.size(3) == dy.size(3), "conv3x3_s2_dgrad: dy has ",
+              dy.size(3), " channels, wd has ", wd.size(3));
+  TORCH_CHECK(wd.size(1) == 3 && wd.size(2) == 3,
+              "conv3x3_s2_dgrad takes 3x3 taps, got ", wd.size(1), "x",
+              wd.size(2));
+  const int64_t n = dy.size(0), cout = dy.size(3), cin = wd.size(0);
+  TORCH_CHECK(cin < (1 << 20) && cout < (1 << 20) &&
+                  conv3x3_s2_supported(n, h, w, (int)cin, (int)cout),
+              "conv3x3_s2_dgrad requires Cin and Cout multiples of 64,"
+              " 1 <= W <= 56, H >= 1 and N*H*W < 2^31, got dy ", dy.sizes(),
+              " wd ", wd.sizes(), " h ", h, " w ", w);
+  TORCH_CHECK(dy.size(1) == (h - 1) / 2 + 1 && dy.size(2) == (w - 1) / 2 + 1,
+              "conv3x3_s2_dgrad: dy ", dy.sizes(),
+              " is not the output of an input of ", h, "x", w);
+  TORCH_CHECK(max_workers >= 0 && max_workers < (1 << 20));
+  DeviceGuard guard(dy.device());
+  auto dx = at::empty({n, h, w, cin}, dy.options());
+  launch_conv3x3_s2_dgrad(bf_ptr(dy), bf_ptr(wd), bf_ptr_mut(dx), (int)n,
+                          (int)h, (int)w, (int)cin, (int)cout,
+                          (int)max_workers, cur_stream());
+  return dx;
+}
+
+std::vector<int64_t> conv3x3_s2_plan_py(int64_t n, int64_t h, int64_t w,
+                                        int64_t cin, int64_t cout,
+                                        int64_t max_workers) {
+  TORCH_CHECK(cin < (1 << 20) && cout < (1 << 20) &&
+              conv3x3_s2_supported(n, h, w, (int)cin, (int)cout));
+  int rows, imgs, tiles, workers;
+  conv3x3_s2_plan((int)n, (int)h, (int)w, (int)cin, (int)cout,
+                  (int)max_workers, &rows, &imgs, &tiles, &workers);
+  return {rows, imgs, tiles, workers};
+}
+
+std::vector<int64_t> conv3x3_s2_dgrad_plan_py(int64_t n, int64_t h, int64_t w,
+                                              int64_t cin, int64_t cout,
+                                              int64_t max_workers) {
+  TORCH_CHECK(cin < (1 << 20) && cout < (1 << 20) &&
+              conv3x3_s2_supported(n, h, w, (int)cin, (int)cout));
+  int rows, imgs, tiles, workers;
+  conv3x3_s2_dgrad_plan((int)n, (int)h, (int)w, (int)cin, (int)cout,
+                        (int)max_workers, &rows, &imgs, &tiles, &workers);
+  return {rows, imgs, tiles, workers};
+}
+
+// ---------------------------------------------------------------------
 // Flash attention (D=64)
 // ---------------------------------------------------------------------
 
@@ -1109,6 +1200,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3_wgrad_plan", &conv3x3_wgrad_plan_py,
         "(rows per band, images per tile, tiles and workers per block "
         "pair) of a conv3x3_wgrad launch",
+        py::arg("n"), py::arg("h"), py::arg("w"), py::arg("cin"),
+        py::arg("cout"), py::arg("max_workers") = 0);
+  m.def("conv3x3_s2", &conv3x3_s2,
+        "3x3 stride-2 pad-1 convolution forward, NHWC bf16",
+        py::arg("x"), py::arg("wt"), py::arg("max_workers") = 0);
+  m.def("conv3x3_s2_plan", &conv3x3_s2_plan_py,
+        "(output rows per band, images per tile, tiles and workers per "
+        "N-block) of a conv3x3_s2 launch on an input of h x w",
+        py::arg("n"), py::arg("h"), py::arg("w"), py::arg("cin"),
+        py::arg("cout"), py::arg("max_workers") = 0);
+  m.def("conv3x3_s2_dgrad", &conv3x3_s2_dgrad,
+        "Data gradient [N,h,w,Cin] of the 3x3 stride-2 pad-1 convolution "
+        "from dy [N,Ho,Wo,Cout] and wd [Cin,3,3,Cout], NHWC bf16",
+        py::arg("dy"), py::arg("wd"), py::arg("h"), py::arg("w"),
+        py::arg("max_workers") = 0);
+  m.def("conv3x3_s2_dgrad_plan", &conv3x3_s2_dgrad_plan_py,
+        "(cell rows per band, dy images per tile, tiles and workers per "
+        "Cin block) of a conv3x3_s2_dgrad launch for an input of h x w",
         py::arg("n"), py::arg("h"), py::arg("w"), py::arg("cin"),
         py::arg("cout"), py::arg("max_workers") = 0);
   m.def("bn_fwd_slab", &bn_fwd_slab,

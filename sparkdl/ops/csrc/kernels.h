@@ -246,6 +246,33 @@ void launch_conv3x3_wgrad(const short* x, const short* dy, float* slabs,
                           short* dw, int n, int h, int w, int cin, int cout,
                           int max_workers, hipStream_t stream);
 
+// 3x3 stride-2 pad-1 convolution (csrc/conv3x3_s2.hip), bf16 NHWC, fp32
+// accumulation, no bias; ho = (h-1)/2 + 1, wo = (w-1)/2 + 1.
+//   forward: y[n,i,j,co] = sum x[n,2i+kh-1,2j+kw-1,ci] * wt[co,kh,kw,ci],
+//            x [n,h,w,cin], wt [cout,3,3,cin], y [n,ho,wo,cout];
+//   dgrad:   dx [n,h,w,cin] from dy [n,ho,wo,cout] and the unflipped
+//            wd [cin,3,3,cout], wd[ci,kh,kw,co] = w[co,ci,kh,kw].
+// Supported: cin and cout multiples of 64, 1 <= w <= 56, h >= 1,
+// n*h*w < 2^31 (h and w are the input's). The plans give the tiling of
+// the ho x wo grid: rows per band and whole images per tile (one of the
+// two is 1 unless a whole image fits a tile), tiles per 64-wide channel
+// block (of cout forward, of cin for dgrad) and persistent workers per
+// block; max_workers > 0 caps the workers. No atomics, no memset, no
+// workspace: the same bits on every run.
+bool conv3x3_s2_supported(long long n, long long h, long long w, int cin,
+                          int cout);
+void conv3x3_s2_plan(int n, int h, int w, int cin, int cout, int max_workers,
+                     int* rows, int* imgs, int* tiles, int* workers);
+void conv3x3_s2_dgrad_plan(int n, int h, int w, int cin, int cout,
+                           int max_workers, int* rows, int* imgs, int* tiles,
+                           int* workers);
+void launch_conv3x3_s2(const short* x, const short* wt, short* y, int n,
+                       int h, int w, int cin, int cout, int max_workers,
+                       hipStream_t stream);
+void launch_conv3x3_s2_dgrad(const short* dy, const short* wd, short* dx,
+                             int n, int h, int w, int cin, int cout,
+                             int max_workers, hipStream_t stream);
+
 // Split-M wgrad GEMM (dW = dZ^T @ X, M-major operands): blocked-LDS
 // tr_b16 fragment path, fp32 output with split atomics. Ships behind
 // SPARKDL_FUSED_WGRAD=1 (Tensile still measures faster).

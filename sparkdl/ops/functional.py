@@ -876,17 +876,86 @@ class _Conv3x3Fn(torch.autograd.Function):
         return dx, dw, None
 
 
-def conv3x3(x, weight, wgrad=None):
-    """``conv2d(x, weight, padding=1)`` for a 3x3 ``weight``
-    [Cout,Cin,3,3] and ``x`` [N,Cin,H,W].
+def conv3x3_s2_supported(n, h, w, cin, cout):
+    """Input shapes the stride-2 kernels take (mirror of
+    csrc/conv3x3_s2.hip)."""
+    return (cin >= 64 and cin % 64 == 0 and cout >= 64 and cout % 64 == 0
+            and n >= 1 and h >= 1 and 1 <= w <= 56 and n * h * w < 2 ** 31)
+
+
+def conv3x3_s2_route(cin, cout, mode=None):
+    """Whether a stride-2 ``Conv3x3`` runs the in-house kernels (forward
+    and dgrad) on inputs that qualify. ``mode`` defaults to
+    SPARKDL_CONV3X3_S2, which defaults to "0" (MIOpen): on only with
+    ``mode != "0"`` and channel counts that are multiples of 64.
+    SPARKDL_CONV3X3 has no say here."""
+    if mode is None:
+        mode = os.environ.get("SPARKDL_CONV3X3_S2", "0")
+    return mode != "0" and conv3x3_s2_supported(1, 1, 1, cin, cout)
+
+
+class _Conv3x3S2Fn(torch.autograd.Function):
+    """y = conv2d(x, weight, stride=2, padding=1) on channels_last bf16
+    tensors. Forward is conv3x3_s2_k, dgrad conv3x3_s2_dgrad_k on the
+    unflipped [Cin,3,3,Cout] weight, wgrad the library's."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        C = _ops.ext()
+        ctx.save_for_backward(x, weight)
+        y = C.conv3x3_s2(x.permute(0, 2, 3, 1),
+                         weight.permute(0, 2, 3, 1).contiguous(), 0)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy):
+        C = _ops.ext()
+        x, weight = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            wd = weight.permute(1, 2, 3, 0).contiguous()
+            dx = C.conv3x3_s2_dgrad(dy.permute(0, 2, 3, 1), wd, x.shape[2],
+                                    x.shape[3], 0).permute(0, 3, 1, 2)
+        if ctx.needs_input_grad[1]:
+            dw = torch.ops.aten.convolution_backward(
+                dy, x, weight, None, [2, 2], [1, 1], [1, 1], False, [0, 0],
+                1, [False, True, False])[1]
+        return dx, dw
+
+
+def conv3x3(x, weight, wgrad=None, stride=1):
+    """``conv2d(x, weight, stride=stride, padding=1)`` for a 3x3
+    ``weight`` [Cout,Cin,3,3], ``x`` [N,Cin,H,W] and ``stride`` 1 or 2.
 
     bf16 channels_last GPU tensors of a supported shape (Cin and Cout
     multiples of 64, W <= 56, N*H*W < 2^31) run the hand-written
-    implicit-GEMM kernel forward and for the data gradient. The weight
-    gradient is the hand-written, deterministic conv3x3_wgrad_k with
-    ``wgrad=True`` and the library's with ``wgrad=False``; ``None`` asks
-    ``conv3x3_wgrad_route()`` (SPARKDL_CONV3X3=all). Everything else is
-    ``torch.nn.functional.conv2d(x, weight, padding=1)`` exactly."""
+    implicit-GEMM kernels forward and for the data gradient:
+    csrc/conv3x3.hip at stride 1, csrc/conv3x3_s2.hip at stride 2. At
+    stride 1 the weight gradient is the hand-written, deterministic
+    conv3x3_wgrad_k with ``wgrad=True`` and the library's with
+    ``wgrad=False``; ``None`` asks ``conv3x3_wgrad_route()``
+    (SPARKDL_CONV3X3=all). At stride 2 it is always the library's, and
+    ``wgrad=True`` raises ``ValueError``. Everything else is
+    ``torch.nn.functional.conv2d(x, weight, stride=stride, padding=1)``
+    exactly."""
+    if stride not in (1, 2):
+        raise ValueError("conv3x3 takes stride 1 or 2, got %r" % (stride,))
+    if stride == 2:
+        if wgrad:
+            raise ValueError(
+                "conv3x3 has no in-house weight gradient at stride 2")
+        if (x.is_cuda and weight.is_cuda and x.dim() == 4
+                and weight.dim() == 4
+                and x.dtype == torch.bfloat16
+                and weight.dtype == torch.bfloat16
+                and tuple(weight.shape[2:]) == (3, 3)
+                and weight.shape[1] == x.shape[1]
+                and x.is_contiguous(memory_format=torch.channels_last)
+                and conv3x3_s2_supported(x.shape[0], x.shape[2], x.shape[3],
+                                         x.shape[1], weight.shape[0])):
+            return _Conv3x3S2Fn.apply(x, weight)
+        return torch.nn.functional.conv2d(x, weight, stride=2, padding=1)
     if (x.is_cuda and weight.is_cuda and x.dim() == 4 and weight.dim() == 4
             and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
             and tuple(weight.shape[2:]) == (3, 3)

@@ -230,15 +230,26 @@ class Conv3x3(nn.Conv2d):
     scripts/conv3x3_bench.py times the kernels against MIOpen at the
     four ResNet-50 sites (profiles/conv3x3_sites.log,
     profiles/conv3x3_wgrad_sites.log; profiles/README.md, "3x3
-    convolution kernel" and "3x3 convolution weight gradient")."""
+    convolution kernel" and "3x3 convolution weight gradient").
+
+    ``SPARKDL_CONV3X3_S2=1``, a switch of its own, moves the stride-2
+    instances with such channel counts (the other 3 of the 16) to the
+    kernels of csrc/conv3x3_s2.hip for forward and dgrad
+    (``functional.conv3x3_s2_route``); their wgrad stays on the library.
+    Opt-in as well: ``scripts/conv3x3_bench.py --stride 2``,
+    profiles/README.md, "3x3 stride-2 convolution kernels"."""
 
     def __init__(self, cin, cout, stride=1):
         super().__init__(cin, cout, 3, stride=stride, padding=1, bias=False)
 
     def forward(self, x):
         if (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
-                and x.is_contiguous(memory_format=torch.channels_last)
-                and F_.conv3x3_route(self.in_channels, self.out_channels,
-                                     self.stride[0])):
-            return F_.conv3x3(x, self.weight.to(x.dtype))
+                and x.is_contiguous(memory_format=torch.channels_last)):
+            if F_.conv3x3_route(self.in_channels, self.out_channels,
+                                self.stride[0]):
+                return F_.conv3x3(x, self.weight.to(x.dtype))
+            if (self.stride == (2, 2)
+                    and F_.conv3x3_s2_route(self.in_channels,
+                                            self.out_channels)):
+                return F_.conv3x3(x, self.weight.to(x.dtype), stride=2)
         return super().forward(x)
