@@ -26,6 +26,12 @@ a cast to fp32 and ``F.cross_entropy`` by default.
 opt-in because the fused loss is computed from fp32 logits where the
 default path rounds them to bf16 first, so the same seed gives a
 slightly different trajectory.
+
+``BertConfig(causal=True)`` makes every self-attention causal (position
+q attends to positions <= q; the flash kernels' triangular schedule on
+the GPU). ``forward_mlm(ids, positions)`` with ``positions`` = every
+token but the last of each row, and the ids shifted by one as labels,
+is then a next-token language model on the same loss code.
 """
 
 import math
@@ -40,7 +46,7 @@ from sparkdl.ops import LayerNorm, Linear, LinearGelu
 class BertConfig:
     def __init__(self, vocab_size=30522, hidden=768, layers=12, heads=12,
                  ffn=3072, max_seq=512, type_vocab=2, dropout=0.1,
-                 fused_dropout_ln=None, fused_mlm_loss=None):
+                 fused_dropout_ln=None, fused_mlm_loss=None, causal=False):
         self.vocab_size = vocab_size
         self.hidden = hidden
         self.layers = layers
@@ -59,6 +65,8 @@ class BertConfig:
             fused_mlm_loss = os.environ.get(
                 "SPARKDL_FUSED_MLM_LOSS", "0") == "1"
         self.fused_mlm_loss = bool(fused_mlm_loss)
+        # left-to-right (decoder-style) self-attention
+        self.causal = bool(causal)
 
 
 class BertEmbeddings(nn.Module):
@@ -87,6 +95,7 @@ class BertSelfAttention(nn.Module):
         self.qkv = Linear(cfg.hidden, 3 * cfg.hidden)
         self.out = Linear(cfg.hidden, cfg.hidden)
         self.drop_p = cfg.dropout
+        self.causal = getattr(cfg, "causal", False)
 
     def forward(self, x, seq_lens=None):
         """seq_lens: optional int32 [B] on x's device — valid length of
@@ -105,16 +114,18 @@ class BertSelfAttention(nn.Module):
             # permute/contiguous copies on the hot path; lengths are
             # read in-kernel (padded tiles skipped, no host sync)
             o = F_.flash_attention_packed(qkv, dropout_p=p,
-                                          seq_lens=seq_lens)
+                                          seq_lens=seq_lens,
+                                          causal=self.causal)
         else:
             q, k, v = qkv.permute(2, 0, 3, 1, 4).unbind(0)  # [B,h,S,d]
             if seq_lens is None:
                 o = nn.functional.scaled_dot_product_attention(
-                    q, k, v, dropout_p=p)
+                    q, k, v, dropout_p=p, is_causal=self.causal)
             else:
                 # same semantics as the kernels (zero padded rows)
                 o = F_.masked_attention_ref(q, k, v, seq_lens,
-                                            dropout_p=p)
+                                            dropout_p=p,
+                                            causal=self.causal)
             o = o.transpose(1, 2).reshape(B, S, H)
         return self.out(o)
 

@@ -856,7 +856,8 @@ static const int* seqlens_ptr(const c10::optional<at::Tensor>& seqlens,
 std::vector<at::Tensor> attn_fwd(const at::Tensor& Q, const at::Tensor& K,
                                  const at::Tensor& V, double dropout_p,
                                  const c10::optional<at::Tensor>& seed,
-                                 const c10::optional<at::Tensor>& seqlens) {
+                                 const c10::optional<at::Tensor>& seqlens,
+                                 bool causal) {
   CHECK_BF16_CUDA(Q);
   CHECK_BF16_CUDA(K);
   CHECK_BF16_CUDA(V);
@@ -876,14 +877,14 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& Q, const at::Tensor& K,
                            cur_stream());
   launch_attn_fwd(bf_ptr(Q), bf_ptr(K), bf_ptr(VT), bf_ptr_mut(O),
                   LSE.data_ptr<float>(), seed_ptr(seed), BH, S, 1, 64,
-                  64, (float)dropout_p, lens, cur_stream());
+                  64, (float)dropout_p, lens, causal, cur_stream());
   return {O, LSE};
 }
 
 std::vector<at::Tensor> attn_fwd_packed(
     const at::Tensor& qkv, double dropout_p,
     const c10::optional<at::Tensor>& seed,
-    const c10::optional<at::Tensor>& seqlens) {
+    const c10::optional<at::Tensor>& seqlens, bool causal) {
   CHECK_BF16_CUDA(qkv);
   TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3 && qkv.size(4) == 64 &&
                   qkv.is_contiguous(),
@@ -903,7 +904,7 @@ std::vector<at::Tensor> attn_fwd_packed(
   launch_attn_fwd(base, base + (long long)H * 64, bf_ptr(VT),
                   bf_ptr_mut(O), LSE.data_ptr<float>(), seed_ptr(seed),
                   B * H, S, H, 3 * H * 64, H * 64, (float)dropout_p, lens,
-                  cur_stream());
+                  causal, cur_stream());
   return {O, LSE};
 }
 
@@ -912,7 +913,8 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& Q, const at::Tensor& K,
                                  const at::Tensor& LSE,
                                  const at::Tensor& Drow, double dropout_p,
                                  const c10::optional<at::Tensor>& seed,
-                                 const c10::optional<at::Tensor>& seqlens) {
+                                 const c10::optional<at::Tensor>& seqlens,
+                                 bool causal) {
   CHECK_BF16_CUDA(Q);
   CHECK_BF16_CUDA(K);
   CHECK_BF16_CUDA(V);
@@ -947,7 +949,7 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& Q, const at::Tensor& K,
                   ktt, LSE.data_ptr<float>(), Drow.data_ptr<float>(),
                   bf_ptr_mut(dQ), bf_ptr_mut(dK), bf_ptr_mut(dV),
                   seed_ptr(seed), BH, S, 1, 64, 64, 64, (float)dropout_p,
-                  lens, cur_stream());
+                  lens, causal, cur_stream());
   return {dQ, dK, dV};
 }
 
@@ -955,7 +957,8 @@ at::Tensor attn_bwd_packed(const at::Tensor& qkv, const at::Tensor& dO,
                            const at::Tensor& LSE, const at::Tensor& Drow,
                            double dropout_p,
                            const c10::optional<at::Tensor>& seed,
-                           const c10::optional<at::Tensor>& seqlens) {
+                           const c10::optional<at::Tensor>& seqlens,
+                           bool causal) {
   CHECK_BF16_CUDA(qkv);
   CHECK_BF16_CUDA(dO);
   CHECK_F32_CUDA(LSE);
@@ -994,7 +997,7 @@ at::Tensor attn_bwd_packed(const at::Tensor& qkv, const at::Tensor& dO,
                   gbase + (long long)H * 64,
                   gbase + (long long)2 * H * 64, seed_ptr(seed), BH, S,
                   H, 3 * H * 64, H * 64, 3 * H * 64, (float)dropout_p,
-                  lens, cur_stream());
+                  lens, causal, cur_stream());
   return dqkv;
 }
 
@@ -1224,24 +1227,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused BatchNorm(+add)(+ReLU) fwd over pre-summed statistics");
   m.def("wgrad_splitk", &wgrad_splitk,
         "Split-M wgrad GEMM (tr_b16 fragment path)");
-  // trailing seqlens defaults to None, so the five-/six-/eight-argument
-  // positional calls from before variable-length support keep working
+  // trailing seqlens defaults to None and causal to false, so the
+  // shorter positional calls from before either argument keep working
   m.def("attn_fwd", &attn_fwd, "Flash attention fwd (D=64, bf16)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dropout_p"),
-        py::arg("seed"), py::arg("seqlens") = py::none());
+        py::arg("seed"), py::arg("seqlens") = py::none(),
+        py::arg("causal") = false);
   m.def("attn_bwd", &attn_bwd, "Flash attention bwd (dQ/dK/dV)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dO"),
         py::arg("lse"), py::arg("drow"), py::arg("dropout_p"),
-        py::arg("seed"), py::arg("seqlens") = py::none());
+        py::arg("seed"), py::arg("seqlens") = py::none(),
+        py::arg("causal") = false);
   m.def("attn_fwd_packed", &attn_fwd_packed,
         "Flash attention fwd over the packed qkv buffer", py::arg("qkv"),
         py::arg("dropout_p"), py::arg("seed"),
-        py::arg("seqlens") = py::none());
+        py::arg("seqlens") = py::none(), py::arg("causal") = false);
   m.def("attn_bwd_packed", &attn_bwd_packed,
         "Flash attention bwd -> packed dqkv", py::arg("qkv"),
         py::arg("dO"), py::arg("lse"), py::arg("drow"),
         py::arg("dropout_p"), py::arg("seed"),
-        py::arg("seqlens") = py::none());
+        py::arg("seqlens") = py::none(), py::arg("causal") = false);
   m.def("gbt_histogram", &gbt_histogram, "GBT g/h histogram (N7)");
   m.def("bn_fwd", &bn_fwd, "Fused BatchNorm(+add)(+ReLU) fwd (bf16 NHWC)");
   m.def("bn_bwd", &bn_bwd, "Fused BatchNorm(+add)(+ReLU) bwd (bf16 NHWC)");

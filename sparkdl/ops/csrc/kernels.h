@@ -306,14 +306,14 @@ void launch_attn_pretranspose(const short* X, short* T, int BH, int S,
 void launch_attn_fwd(const short* Q, const short* K, const short* VT,
                      short* O, float* LSE, const long long* seed, int BH,
                      int S, int H, int rs, int ors, float dropout_p,
-                     const int* seqlens, hipStream_t stream);
+                     const int* seqlens, bool causal, hipStream_t stream);
 void launch_attn_bwd(const short* Q, const short* K, const short* V,
                      const short* dO, const short* QT, const short* DOT,
                      const short* KT, const float* LSE, const float* Drow,
                      short* dQ, short* dK, short* dV,
                      const long long* seed, int BH, int S, int H, int rs,
                      int ors, int grs, float dropout_p,
-                     const int* seqlens, hipStream_t stream);
+                     const int* seqlens, bool causal, hipStream_t stream);
 
 // GBT per-(node,feature,bin) gradient/hessian histograms
 // (SURVEY.md §2.2 N7). bmap: per-block {node, f0, start, count} over a

@@ -27,9 +27,13 @@ def bias_gelu_ref(x, bias):
         x.float() + bias.float(), approximate="none").to(x.dtype)
 
 
-def masked_attention_ref(q, k, v, seq_lens, dropout_p=0.0):
+def masked_attention_ref(q, k, v, seq_lens, dropout_p=0.0, causal=False):
     """Attention over a right-padded batch: row ``n`` of the leading
     dim holds ``seq_lens[n]`` valid tokens at positions ``[0, len)``.
+    ``seq_lens=None`` means no padding (every length is ``S``).
+    ``causal=True`` adds the lower-triangular mask of self-attention:
+    query ``q`` attends to key ``k`` iff ``k <= q`` (and ``k < len``),
+    applied the same way as the key mask.
 
     q/k/v: ``[N, ..., S, d]`` (``[BH,S,d]`` or ``[B,h,S,d]``); seq_lens:
     integer ``[N]`` (clamped into ``[0, S]``). For ``q < len``:
@@ -45,11 +49,16 @@ def masked_attention_ref(q, k, v, seq_lens, dropout_p=0.0):
     padding."""
     S, d = q.shape[-2], q.shape[-1]
     qf, kf, vf = q.float(), k.float(), v.float()
+    if seq_lens is None:
+        seq_lens = torch.full((q.shape[0],), S)
     lens = torch.as_tensor(seq_lens, device=q.device).clamp(0, S)
     lens = lens.reshape((-1,) + (1,) * (q.dim() - 2))
     valid = torch.arange(S, device=q.device) < lens    # [N, ..., S]
     kmask = valid.unsqueeze(-2)
     qmask = valid.unsqueeze(-1)
+    if causal:  # [N, ..., S, S]: keys at or before the query
+        kmask = kmask & torch.ones(
+            S, S, dtype=torch.bool, device=q.device).tril()
     # fp32 throughout, also when called under autocast (the fill value
     # does not fit a 16-bit score matrix)
     with torch.autocast(q.device.type, enabled=False):
@@ -523,10 +532,11 @@ class _FlashAttnFn(torch.autograd.Function):
     """O = softmax(Q K^T / sqrt(64)) V with optional attention-prob
     dropout. q/k/v: [BH, S, 64] bf16 contiguous, S % 64 == 0.
     seq_lens (optional): int32 [BH] on the same device — right-padded
-    rows, masked_attention_ref semantics; it gets no gradient."""
+    rows, masked_attention_ref semantics; it gets no gradient.
+    causal: key k is attended to from query q iff k <= q."""
 
     @staticmethod
-    def forward(ctx, q, k, v, dropout_p, seq_lens=None):
+    def forward(ctx, q, k, v, dropout_p, seq_lens=None, causal=False):
         C = _ops.ext()
         seed = None
         if dropout_p > 0:
@@ -535,11 +545,13 @@ class _FlashAttnFn(torch.autograd.Function):
             # the backward must replay this step's seed even if later
             # steps advanced the counter
             seed = seed.clone()
-        o, lse = C.attn_fwd(q, k, v, float(dropout_p), seed, seq_lens)
+        o, lse = C.attn_fwd(q, k, v, float(dropout_p), seed, seq_lens,
+                            bool(causal))
         ctx.save_for_backward(q, k, v, o, lse,
                               seed if seed is not None else
                               torch.empty(0), seq_lens)
         ctx.dropout_p = float(dropout_p)
+        ctx.causal = bool(causal)
         return o
 
     @staticmethod
@@ -552,18 +564,22 @@ class _FlashAttnFn(torch.autograd.Function):
         # D_i = rowsum(dO o O), fp32 (flash backward precompute)
         drow = (do.float() * o.float()).sum(-1)
         dq, dk, dv = C.attn_bwd(q, k, v, do, lse, drow, ctx.dropout_p,
-                                seed, seq_lens)
-        return dq, dk, dv, None, None
+                                seed, seq_lens, ctx.causal)
+        return dq, dk, dv, None, None, None
 
 
-def flash_attention(q, k, v, dropout_p=0.0, seq_lens=None):
+def flash_attention(q, k, v, dropout_p=0.0, seq_lens=None, causal=False):
     """[B, h, S, d] attention through the hand-written kernels; the
     caller checks flash_attention_ok first.
 
     seq_lens (optional): int32 [B] on q's device, the valid length of
     each right-padded batch row (masked_attention_ref semantics: padded
     query rows come back exactly zero). The lengths are only ever read
-    on the device, so the call stays sync-free and graph-capturable."""
+    on the device, so the call stays sync-free and graph-capturable.
+
+    causal=True: query q attends to keys k <= q only (self-attention,
+    and k < len with seq_lens), through kernels that never stage the
+    tiles above the diagonal."""
     B, h, S, d = q.shape
     q3 = q.reshape(B * h, S, d).contiguous()
     k3 = k.reshape(B * h, S, d).contiguous()
@@ -571,7 +587,7 @@ def flash_attention(q, k, v, dropout_p=0.0, seq_lens=None):
     if seq_lens is not None:
         # the [BH,S,64] kernels index lengths per bh
         seq_lens = seq_lens.view(B, 1).expand(B, h).reshape(B * h)
-    o = _FlashAttnFn.apply(q3, k3, v3, dropout_p, seq_lens)
+    o = _FlashAttnFn.apply(q3, k3, v3, dropout_p, seq_lens, causal)
     return o.view(B, h, S, d)
 
 
@@ -588,18 +604,20 @@ class _FlashAttnPackedFn(torch.autograd.Function):
     contiguous copies anywhere around the attention."""
 
     @staticmethod
-    def forward(ctx, qkv, dropout_p, seq_lens=None):
+    def forward(ctx, qkv, dropout_p, seq_lens=None, causal=False):
         C = _ops.ext()
         seed = None
         if dropout_p > 0:
             seed = _attn_seed_tensor(qkv.device)
             seed.add_(1)
             seed = seed.clone()
-        o, lse = C.attn_fwd_packed(qkv, float(dropout_p), seed, seq_lens)
+        o, lse = C.attn_fwd_packed(qkv, float(dropout_p), seed, seq_lens,
+                                   bool(causal))
         ctx.save_for_backward(qkv, o, lse,
                               seed if seed is not None else
                               torch.empty(0), seq_lens)
         ctx.dropout_p = float(dropout_p)
+        ctx.causal = bool(causal)
         return o
 
     @staticmethod
@@ -615,11 +633,12 @@ class _FlashAttnPackedFn(torch.autograd.Function):
         drow = (do.float() * o.float()).view(B, S, H, 64).sum(-1) \
             .transpose(1, 2).reshape(B * H, S).contiguous()
         dqkv = C.attn_bwd_packed(qkv, do, lse, drow, ctx.dropout_p, seed,
-                                 seq_lens)
-        return dqkv, None, None
+                                 seq_lens, ctx.causal)
+        return dqkv, None, None, None
 
 
-def flash_attention_packed(qkv, dropout_p=0.0, seq_lens=None):
+def flash_attention_packed(qkv, dropout_p=0.0, seq_lens=None,
+                           causal=False):
     """qkv: [B, S, 3, H, 64] bf16 contiguous -> O [B, S, H*64].
 
     seq_lens (optional): int32 [B] on qkv's device, the valid length of
@@ -630,8 +649,14 @@ def flash_attention_packed(qkv, dropout_p=0.0, seq_lens=None):
     only: no host sync, graph-capturable, and the tensor may be
     refilled in place between graph replays. seqlens_from_mask turns an
     attention_mask into lengths (its validation syncs; passing seq_lens
-    is the sync-free path)."""
-    return _FlashAttnPackedFn.apply(qkv.contiguous(), dropout_p, seq_lens)
+    is the sync-free path).
+
+    causal=True: position q attends to positions k <= q only (and
+    k < len_b), the mask of a left-to-right language model. The causal
+    kernels walk the lower triangle of 64x64 tiles alone (36 of the 64
+    tile pairs at S=512) and mask inside the diagonal tiles."""
+    return _FlashAttnPackedFn.apply(qkv.contiguous(), dropout_p, seq_lens,
+                                    causal)
 
 
 def _conv_gemm(a2d, w):
