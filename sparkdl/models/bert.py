@@ -32,6 +32,13 @@ q attends to positions <= q; the flash kernels' triangular schedule on
 the GPU). ``forward_mlm(ids, positions)`` with ``positions`` = every
 token but the last of each row, and the ids shifted by one as labels,
 is then a next-token language model on the same loss code.
+
+Heads of width 64 and 128 (``hidden // heads``) have flash kernels. At
+width 128 a call without ``seq_lens`` takes them when
+SPARKDL_FLASH_D128 is "1" (see ``_FLASH_D128_DEFAULT`` and
+profiles/README.md, "Flash attention, 128-wide heads"); a call with
+``seq_lens`` always does: its only alternative is the composed
+reference, which materialises the [B,h,S,S] fp32 scores.
 """
 
 import math
@@ -87,7 +94,16 @@ class BertEmbeddings(nn.Module):
         return self.drop(self.ln(h))
 
 
+# Value of SPARKDL_FLASH_D128 when it is unset: whether 128-wide heads
+# take the flash kernels without seq_lens (decided by the measurement in
+# profiles/attn_d128.log against scaled_dot_product_attention).
+_FLASH_D128_DEFAULT = "0"
+
+
 class BertSelfAttention(nn.Module):
+    # False sends every call through the library / composed branch
+    use_flash = True
+
     def __init__(self, cfg):
         super().__init__()
         self.heads = cfg.heads
@@ -106,8 +122,12 @@ class BertSelfAttention(nn.Module):
         B, S, H = x.shape
         qkv = self.qkv(x).view(B, S, 3, self.heads, self.head_dim)
         p = self.drop_p if self.training else 0.0
-        if (qkv.is_cuda and qkv.dtype == torch.bfloat16
-                and self.head_dim == 64 and S % 64 == 0):
+        wide_ok = seq_lens is not None or os.environ.get(
+            "SPARKDL_FLASH_D128", _FLASH_D128_DEFAULT) == "1"
+        if (self.use_flash and qkv.is_cuda and qkv.dtype == torch.bfloat16
+                and (self.head_dim == 64
+                     or (self.head_dim == 128 and wide_ok))
+                and S % 64 == 0):
             # hand-written CDNA4 flash kernels (fwd+bwd, in-kernel
             # dropout), reading the packed qkv buffer with strided rows
             # and writing O as [B,S,H] directly — no Triton and no

@@ -825,7 +825,7 @@ std::vector<int64_t> conv3x3_s2_dgrad_plan_py(int64_t n, int64_t h, int64_t w,
 }
 
 // ---------------------------------------------------------------------
-// Flash attention (D=64)
+// Flash attention (D=64 and D=128)
 // ---------------------------------------------------------------------
 
 static const long long* seed_ptr(const c10::optional<at::Tensor>& seed) {
@@ -837,7 +837,7 @@ static const long long* seed_ptr(const c10::optional<at::Tensor>& seed) {
 
 // Per-sequence lengths of a right-padded batch: int32 on the data's
 // device, one entry per batch row (`rows` = B for the packed layout, BH
-// for plain [BH,S,64]). The VALUES stay on the device (the kernels
+// for plain [BH,S,D]). The VALUES stay on the device (the kernels
 // clamp them into [0,S]); only the metadata is validated here.
 static const int* seqlens_ptr(const c10::optional<at::Tensor>& seqlens,
                               const at::Tensor& like, int64_t rows) {
@@ -853,6 +853,10 @@ static const int* seqlens_ptr(const c10::optional<at::Tensor>& seqlens,
   return seqlens->data_ptr<int>();
 }
 
+// Head widths with kernels: 64 (attention.hip, attention_causal.hip) and
+// 128 (attention_d128.hip).
+static bool attn_width_ok(int64_t d) { return d == 64 || d == 128; }
+
 std::vector<at::Tensor> attn_fwd(const at::Tensor& Q, const at::Tensor& K,
                                  const at::Tensor& V, double dropout_p,
                                  const c10::optional<at::Tensor>& seed,
@@ -861,9 +865,9 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& Q, const at::Tensor& K,
   CHECK_BF16_CUDA(Q);
   CHECK_BF16_CUDA(K);
   CHECK_BF16_CUDA(V);
-  TORCH_CHECK(Q.dim() == 3 && Q.size(2) == 64 && Q.sizes() == K.sizes() &&
-                  Q.sizes() == V.sizes(),
-              "attn_fwd expects [BH, S, 64] bf16 q/k/v");
+  TORCH_CHECK(Q.dim() == 3 && attn_width_ok(Q.size(2)) &&
+                  Q.sizes() == K.sizes() && Q.sizes() == V.sizes(),
+              "attn_fwd expects [BH, S, 64] or [BH, S, 128] bf16 q/k/v");
   const int BH = (int)Q.size(0), S = (int)Q.size(1);
   TORCH_CHECK(S % 64 == 0, "attn_fwd requires S % 64 == 0");
   TORCH_CHECK(dropout_p == 0.0 || seed.has_value(),
@@ -872,6 +876,13 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& Q, const at::Tensor& K,
   DeviceGuard guard(Q.device());
   auto O = at::empty_like(Q);
   auto LSE = at::empty({BH, S}, Q.options().dtype(at::kFloat));
+  if (Q.size(2) == 128) {  // transposes on the LDS read: no scratch
+    launch_attn_d128_fwd(bf_ptr(Q), bf_ptr(K), bf_ptr(V), bf_ptr_mut(O),
+                         LSE.data_ptr<float>(), seed_ptr(seed), BH, S, 1,
+                         128, 128, (float)dropout_p, lens, causal,
+                         cur_stream());
+    return {O, LSE};
+  }
   auto VT = at::empty({BH, 64, S}, Q.options());
   launch_attn_pretranspose(bf_ptr(V), bf_ptr_mut(VT), BH, S, 1, 64,
                            cur_stream());
@@ -886,18 +897,27 @@ std::vector<at::Tensor> attn_fwd_packed(
     const c10::optional<at::Tensor>& seed,
     const c10::optional<at::Tensor>& seqlens, bool causal) {
   CHECK_BF16_CUDA(qkv);
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3 && qkv.size(4) == 64 &&
-                  qkv.is_contiguous(),
-              "attn_fwd_packed expects contiguous [B,S,3,H,64] bf16");
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3 &&
+                  attn_width_ok(qkv.size(4)) && qkv.is_contiguous(),
+              "attn_fwd_packed expects contiguous [B,S,3,H,64] or "
+              "[B,S,3,H,128] bf16");
   const int B = (int)qkv.size(0), S = (int)qkv.size(1),
-            H = (int)qkv.size(3);
+            H = (int)qkv.size(3), D = (int)qkv.size(4);
   TORCH_CHECK(S % 64 == 0, "attn requires S % 64 == 0");
   TORCH_CHECK(dropout_p == 0.0 || seed.has_value());
   const int* lens = seqlens_ptr(seqlens, qkv, B);
   DeviceGuard guard(qkv.device());
-  auto O = at::empty({B, S, H * 64}, qkv.options());
+  auto O = at::empty({B, S, H * D}, qkv.options());
   auto LSE = at::empty({B * H, S}, qkv.options().dtype(at::kFloat));
   const short* base = bf_ptr(qkv);
+  if (D == 128) {
+    launch_attn_d128_fwd(base, base + (long long)H * 128,
+                         base + (long long)2 * H * 128, bf_ptr_mut(O),
+                         LSE.data_ptr<float>(), seed_ptr(seed), B * H, S, H,
+                         3 * H * 128, H * 128, (float)dropout_p, lens,
+                         causal, cur_stream());
+    return {O, LSE};
+  }
   auto VT = at::empty({B * H, 64, S}, qkv.options());
   launch_attn_pretranspose(base + (long long)2 * H * 64, bf_ptr_mut(VT),
                            B * H, S, H, 3 * H * 64, cur_stream());
@@ -922,10 +942,12 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& Q, const at::Tensor& K,
   CHECK_F32_CUDA(LSE);
   CHECK_F32_CUDA(Drow);
   // same shape contract as attn_fwd: the kernels index every operand
-  // with Q's [BH, S, 64] extents
-  TORCH_CHECK(Q.dim() == 3 && Q.size(2) == 64 && Q.sizes() == K.sizes() &&
-                  Q.sizes() == V.sizes() && Q.sizes() == dO.sizes(),
-              "attn_bwd expects [BH, S, 64] bf16 q/k/v/dO of equal sizes");
+  // with Q's [BH, S, D] extents
+  TORCH_CHECK(Q.dim() == 3 && attn_width_ok(Q.size(2)) &&
+                  Q.sizes() == K.sizes() && Q.sizes() == V.sizes() &&
+                  Q.sizes() == dO.sizes(),
+              "attn_bwd expects [BH, S, 64] or [BH, S, 128] bf16 q/k/v/dO "
+              "of equal sizes");
   const int BH = (int)Q.size(0), S = (int)Q.size(1);
   TORCH_CHECK(S % 64 == 0, "attn_bwd requires S % 64 == 0");
   TORCH_CHECK(LSE.dim() == 2 && LSE.size(0) == BH && LSE.size(1) == S &&
@@ -938,6 +960,14 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& Q, const at::Tensor& K,
   auto dQ = at::empty_like(Q);
   auto dK = at::empty_like(K);
   auto dV = at::empty_like(V);
+  if (Q.size(2) == 128) {
+    launch_attn_d128_bwd(bf_ptr(Q), bf_ptr(K), bf_ptr(V), bf_ptr(dO),
+                         LSE.data_ptr<float>(), Drow.data_ptr<float>(),
+                         bf_ptr_mut(dQ), bf_ptr_mut(dK), bf_ptr_mut(dV),
+                         seed_ptr(seed), BH, S, 1, 128, 128, 128,
+                         (float)dropout_p, lens, causal, cur_stream());
+    return {dQ, dK, dV};
+  }
   auto T3 = at::empty({3, BH, 64, S}, Q.options());
   short* qt = bf_ptr_mut(T3);
   short* dot = qt + (long long)BH * 64 * S;
@@ -963,14 +993,16 @@ at::Tensor attn_bwd_packed(const at::Tensor& qkv, const at::Tensor& dO,
   CHECK_BF16_CUDA(dO);
   CHECK_F32_CUDA(LSE);
   CHECK_F32_CUDA(Drow);
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3 && qkv.size(4) == 64,
-              "attn_bwd_packed expects contiguous [B,S,3,H,64] bf16");
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3 &&
+                  attn_width_ok(qkv.size(4)),
+              "attn_bwd_packed expects contiguous [B,S,3,H,64] or "
+              "[B,S,3,H,128] bf16");
   const int B = (int)qkv.size(0), S = (int)qkv.size(1),
-            H = (int)qkv.size(3);
+            H = (int)qkv.size(3), D = (int)qkv.size(4);
   TORCH_CHECK(S % 64 == 0, "attn requires S % 64 == 0");
   TORCH_CHECK(dO.dim() == 3 && dO.size(0) == B && dO.size(1) == S &&
-                  dO.size(2) == (int64_t)H * 64,
-              "attn_bwd_packed expects dO [B, S, H*64]");
+                  dO.size(2) == (int64_t)H * D,
+              "attn_bwd_packed expects dO [B, S, H*64] or [B, S, H*128]");
   TORCH_CHECK(LSE.dim() == 2 && LSE.size(0) == (int64_t)B * H &&
                   LSE.size(1) == S && LSE.sizes() == Drow.sizes(),
               "attn_bwd_packed expects [B*H, S] fp32 LSE and Drow");
@@ -982,6 +1014,16 @@ at::Tensor attn_bwd_packed(const at::Tensor& qkv, const at::Tensor& dO,
   const short* base = bf_ptr(qkv);
   short* gbase = bf_ptr_mut(dqkv);
   const int BH = B * H;
+  if (D == 128) {
+    launch_attn_d128_bwd(base, base + (long long)H * 128,
+                         base + (long long)2 * H * 128, bf_ptr(dO),
+                         LSE.data_ptr<float>(), Drow.data_ptr<float>(),
+                         gbase, gbase + (long long)H * 128,
+                         gbase + (long long)2 * H * 128, seed_ptr(seed), BH,
+                         S, H, 3 * H * 128, H * 128, 3 * H * 128,
+                         (float)dropout_p, lens, causal, cur_stream());
+    return dqkv;
+  }
   auto T3 = at::empty({3, BH, 64, S}, qkv.options());
   short* qt = bf_ptr_mut(T3);
   short* dot = qt + (long long)BH * 64 * S;
@@ -1229,7 +1271,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Split-M wgrad GEMM (tr_b16 fragment path)");
   // trailing seqlens defaults to None and causal to false, so the
   // shorter positional calls from before either argument keep working
-  m.def("attn_fwd", &attn_fwd, "Flash attention fwd (D=64, bf16)",
+  m.def("attn_fwd", &attn_fwd, "Flash attention fwd (D=64 or 128, bf16)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dropout_p"),
         py::arg("seed"), py::arg("seqlens") = py::none(),
         py::arg("causal") = false);

@@ -315,6 +315,23 @@ void launch_attn_bwd(const short* Q, const short* K, const short* V,
                      int ors, int grs, float dropout_p,
                      const int* seqlens, bool causal, hipStream_t stream);
 
+// Flash attention, D=128 heads (attention_d128.hip): the same contract
+// over [BH, S, 128] bf16 (strides, seqlens, causal, LSE, dropout), with
+// 1/sqrt(128) applied to the fp32 scores. No pre-transposed operands:
+// the kernels transpose on the LDS read, so there is no scratch to build.
+void launch_attn_d128_fwd(const short* Q, const short* K, const short* V,
+                          short* O, float* LSE, const long long* seed,
+                          int BH, int S, int H, int rs, int ors,
+                          float dropout_p, const int* seqlens, bool causal,
+                          hipStream_t stream);
+void launch_attn_d128_bwd(const short* Q, const short* K, const short* V,
+                          const short* dO, const float* LSE,
+                          const float* Drow, short* dQ, short* dK,
+                          short* dV, const long long* seed, int BH, int S,
+                          int H, int rs, int ors, int grs, float dropout_p,
+                          const int* seqlens, bool causal,
+                          hipStream_t stream);
+
 // GBT per-(node,feature,bin) gradient/hessian histograms
 // (SURVEY.md §2.2 N7). bmap: per-block {node, f0, start, count} over a
 // node-sorted row_list; hist: fp32 [n_nodes, F, 256, 2], pre-zeroed.

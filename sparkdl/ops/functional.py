@@ -508,7 +508,8 @@ def linear_gelu_fused_ok(x, weight):
 
 # ---------------------------------------------------------------------------
 # Flash attention (SURVEY.md N6 attention GEMMs) — hand-written fwd+bwd,
-# D=64 heads, replaces torch SDPA (aotriton) on the BERT hot path.
+# D=64 and D=128 heads, replaces torch SDPA (aotriton) on the BERT hot
+# path. The head width is taken from the tensors' last dimension.
 # ---------------------------------------------------------------------------
 
 _attn_seed = {}
@@ -529,8 +530,9 @@ def _attn_seed_tensor(device):
 
 
 class _FlashAttnFn(torch.autograd.Function):
-    """O = softmax(Q K^T / sqrt(64)) V with optional attention-prob
-    dropout. q/k/v: [BH, S, 64] bf16 contiguous, S % 64 == 0.
+    """O = softmax(Q K^T / sqrt(D)) V with optional attention-prob
+    dropout. q/k/v: [BH, S, D] bf16 contiguous, D in (64, 128),
+    S % 64 == 0.
     seq_lens (optional): int32 [BH] on the same device — right-padded
     rows, masked_attention_ref semantics; it gets no gradient.
     causal: key k is attended to from query q iff k <= q."""
@@ -569,8 +571,8 @@ class _FlashAttnFn(torch.autograd.Function):
 
 
 def flash_attention(q, k, v, dropout_p=0.0, seq_lens=None, causal=False):
-    """[B, h, S, d] attention through the hand-written kernels; the
-    caller checks flash_attention_ok first.
+    """[B, h, S, d] attention through the hand-written kernels, d = 64
+    or 128; the caller checks flash_attention_ok first.
 
     seq_lens (optional): int32 [B] on q's device, the valid length of
     each right-padded batch row (masked_attention_ref semantics: padded
@@ -585,7 +587,7 @@ def flash_attention(q, k, v, dropout_p=0.0, seq_lens=None, causal=False):
     k3 = k.reshape(B * h, S, d).contiguous()
     v3 = v.reshape(B * h, S, d).contiguous()
     if seq_lens is not None:
-        # the [BH,S,64] kernels index lengths per bh
+        # the [BH,S,d] kernels index lengths per bh
         seq_lens = seq_lens.view(B, 1).expand(B, h).reshape(B * h)
     o = _FlashAttnFn.apply(q3, k3, v3, dropout_p, seq_lens, causal)
     return o.view(B, h, S, d)
@@ -593,15 +595,15 @@ def flash_attention(q, k, v, dropout_p=0.0, seq_lens=None, causal=False):
 
 def flash_attention_ok(q):
     return (q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 4
-            and q.shape[-1] == 64 and q.shape[-2] % 64 == 0)
+            and q.shape[-1] in (64, 128) and q.shape[-2] % 64 == 0)
 
 
 class _FlashAttnPackedFn(torch.autograd.Function):
     """Zero-copy BERT attention: reads the packed qkv buffer
-    [B,S,3,H,64] (the qkv Linear's output, viewed) with strided kernel
-    rows, writes O directly as [B,S,H*64], and the backward emits the
-    packed dqkv the qkv Linear's backward consumes — no permute/
-    contiguous copies anywhere around the attention."""
+    [B,S,3,H,D] (the qkv Linear's output, viewed; D = 64 or 128) with
+    strided kernel rows, writes O directly as [B,S,H*D], and the backward
+    emits the packed dqkv the qkv Linear's backward consumes — no
+    permute/contiguous copies anywhere around the attention."""
 
     @staticmethod
     def forward(ctx, qkv, dropout_p, seq_lens=None, causal=False):
@@ -627,10 +629,10 @@ class _FlashAttnPackedFn(torch.autograd.Function):
         if seed.numel() == 0:
             seed = None
         do = do.contiguous()
-        B, S, HD = o.shape
-        H = HD // 64
+        B, S, _ = o.shape
+        H, D = qkv.shape[3], qkv.shape[4]
         # D_i = rowsum(dO o O) per (b,h,s): [B,S,H] -> [B*H, S]
-        drow = (do.float() * o.float()).view(B, S, H, 64).sum(-1) \
+        drow = (do.float() * o.float()).view(B, S, H, D).sum(-1) \
             .transpose(1, 2).reshape(B * H, S).contiguous()
         dqkv = C.attn_bwd_packed(qkv, do, lse, drow, ctx.dropout_p, seed,
                                  seq_lens, ctx.causal)
@@ -639,7 +641,9 @@ class _FlashAttnPackedFn(torch.autograd.Function):
 
 def flash_attention_packed(qkv, dropout_p=0.0, seq_lens=None,
                            causal=False):
-    """qkv: [B, S, 3, H, 64] bf16 contiguous -> O [B, S, H*64].
+    """qkv: [B, S, 3, H, D] bf16 contiguous, D = 64 or 128 (dispatched on
+    the tensor) -> O [B, S, H*D]. The 128-wide kernels transpose their
+    operands on the LDS read and allocate no scratch.
 
     seq_lens (optional): int32 [B] on qkv's device, the valid length of
     each right-padded batch row. Row b attends over keys [0, len_b);
