@@ -39,6 +39,17 @@ SPARKDL_FLASH_D128 is "1" (see ``_FLASH_D128_DEFAULT`` and
 profiles/README.md, "Flash attention, 128-wide heads"); a call with
 ``seq_lens`` always does: its only alternative is the composed
 reference, which materialises the [B,h,S,S] fp32 scores.
+
+Unpadded batches: ``encode``, ``forward``, ``forward_mlm`` and
+``mlm_loss`` take ``cu_seqlens`` (int32 ``[B+1]``, with ``max_seqlen``
+defaulting to ``cfg.max_seq``). ``ids`` and ``token_type`` are then
+one-dimensional ``[T]``, the sequences back to back, the hidden states
+are ``[T, hidden]`` and ``positions`` index that flat axis: every GEMM,
+LayerNorm and bias+GELU runs on the real tokens only, and attention is
+``ops.flash_attention_unpadded`` (bf16 on the GPU, heads of width 64 or
+128; elsewhere the composed ``ops.unpadded_attention_ref``).
+``bert_pretrain_step(..., seq_lens=..., unpad=True)`` packs its batch
+once and trains this way.
 """
 
 import math
@@ -85,9 +96,18 @@ class BertEmbeddings(nn.Module):
         self.ln = LayerNorm(cfg.hidden, eps=1e-12)
         self.drop = nn.Dropout(cfg.dropout)
 
-    def forward(self, ids, token_type=None):
-        B, S = ids.shape
-        pos = torch.arange(S, device=ids.device).unsqueeze(0)
+    def forward(self, ids, token_type=None, cu_seqlens=None):
+        if cu_seqlens is not None:
+            # ids [T]: a token's position is its offset inside its
+            # sequence, found on the device (no sync). Spare tokens
+            # count on from cu[B]; clamped into the table.
+            tok = torch.arange(ids.shape[0], device=ids.device)
+            cu = cu_seqlens.long()
+            seq = torch.searchsorted(cu[1:].contiguous(), tok, right=True)
+            pos = (tok - cu[seq]).clamp(0, self.position.num_embeddings - 1)
+        else:
+            B, S = ids.shape
+            pos = torch.arange(S, device=ids.device).unsqueeze(0)
         h = self.word(ids) + self.position(pos)
         if token_type is not None:
             h = h + self.token_type(token_type)
@@ -113,12 +133,30 @@ class BertSelfAttention(nn.Module):
         self.drop_p = cfg.dropout
         self.causal = getattr(cfg, "causal", False)
 
-    def forward(self, x, seq_lens=None):
+    def _forward_unpadded(self, x, cu_seqlens, max_seqlen):
+        """x [T, hidden], the sequences back to back (cu_seqlens int32
+        [B+1]); the attention output at spare tokens is exactly zero."""
+        from sparkdl.ops import functional as F_
+        qkv = self.qkv(x).view(x.shape[0], 3, self.heads, self.head_dim)
+        p = self.drop_p if self.training else 0.0
+        if self.use_flash and F_.flash_attention_unpadded_ok(qkv):
+            # no S % 64 condition and no opt-in at width 128: the only
+            # alternative is the composed reference
+            o = F_.flash_attention_unpadded(qkv, cu_seqlens, max_seqlen,
+                                            dropout_p=p, causal=self.causal)
+        else:
+            o = F_.unpadded_attention_ref(qkv, cu_seqlens, dropout_p=p,
+                                          causal=self.causal)
+        return self.out(o)
+
+    def forward(self, x, seq_lens=None, cu_seqlens=None, max_seqlen=None):
         """seq_lens: optional int32 [B] on x's device — valid length of
         each right-padded row. Padded keys are never attended to and
         the attention output at padded positions is exactly zero, on
         the flash path and on the fallback path alike."""
         from sparkdl.ops import functional as F_
+        if cu_seqlens is not None:
+            return self._forward_unpadded(x, cu_seqlens, max_seqlen)
         B, S, H = x.shape
         qkv = self.qkv(x).view(B, S, 3, self.heads, self.head_dim)
         p = self.drop_p if self.training else 0.0
@@ -167,11 +205,15 @@ class BertLayer(nn.Module):
         return F_.dropout_add_layer_norm(sub, x, ln.weight, ln.bias,
                                          self.drop.p, self.training, ln.eps)
 
-    def forward(self, x, seq_lens=None):
+    def forward(self, x, seq_lens=None, cu_seqlens=None, max_seqlen=None):
+        if cu_seqlens is not None:  # x [T, hidden]
+            a = self.attn(x, cu_seqlens=cu_seqlens, max_seqlen=max_seqlen)
+        else:
+            a = self.attn(x, seq_lens)
         if self.fused_dropout_ln:
-            x = self._tail(self.ln1, self.attn(x, seq_lens), x)
+            x = self._tail(self.ln1, a, x)
             return self._tail(self.ln2, self.ffn_out(self.ffn_in(x)), x)
-        x = self.ln1(x + self.drop(self.attn(x, seq_lens)))
+        x = self.ln1(x + self.drop(a))
         x = self.ln2(x + self.drop(self.ffn_out(self.ffn_in(x))))
         return x
 
@@ -214,9 +256,28 @@ class BertBase(nn.Module):
         return torch.as_tensor(seq_lens).to(
             device=ids.device, dtype=torch.int32).contiguous()
 
+    def _cu_seqlens(self, ids, attention_mask, seq_lens, cu_seqlens,
+                    max_seqlen):
+        """Check the unpadded arguments; -> (int32 cu_seqlens on ids'
+        device, max_seqlen)."""
+        if attention_mask is not None or seq_lens is not None:
+            raise ValueError("cu_seqlens describes an unpadded batch: pass "
+                             "no attention_mask or seq_lens with it")
+        if ids.dim() != 1:
+            raise ValueError("with cu_seqlens, ids is one-dimensional [T]")
+        cu = torch.as_tensor(cu_seqlens).to(
+            device=ids.device, dtype=torch.int32).contiguous()
+        return cu, int(self.cfg.max_seq if max_seqlen is None
+                       else max_seqlen)
+
     def encode(self, ids, token_type=None, *, attention_mask=None,
-               seq_lens=None):
+               seq_lens=None, cu_seqlens=None, max_seqlen=None):
         """Hidden states [B, S, hidden].
+
+        Unpadded batches: ``ids`` (and ``token_type``) ``[T]`` with the
+        sequences back to back and ``cu_seqlens`` int ``[B+1]`` give
+        hidden states ``[T, hidden]``; tokens from ``cu[B]`` on are
+        spare capacity with unspecified but finite hidden states.
 
         Variable-length batches are right-padded: pass either
         ``attention_mask`` ([B,S], 1 = token, each row a prefix of
@@ -225,15 +286,20 @@ class BertBase(nn.Module):
         then never attended to, so hidden states at valid positions do
         not depend on the padding. Hidden states AT padded positions
         are unspecified but finite."""
-        seq_lens = self._seq_lens(ids, attention_mask, seq_lens)
-        h = self.embeddings(ids, token_type)
+        if cu_seqlens is not None:
+            cu_seqlens, max_seqlen = self._cu_seqlens(
+                ids, attention_mask, seq_lens, cu_seqlens, max_seqlen)
+            seq_lens = None
+        else:
+            seq_lens = self._seq_lens(ids, attention_mask, seq_lens)
+        h = self.embeddings(ids, token_type, cu_seqlens)
         # Keep the residual stream in the autocast compute dtype (bf16) so
         # every LayerNorm / bias+GELU hits the CDNA4 kernels; embeddings
         # and type-promoted residual adds would otherwise pin it to fp32.
         if h.is_cuda and torch.is_autocast_enabled():
             h = h.to(torch.get_autocast_dtype("cuda"))
         for layer in self.encoder:
-            h = layer(h, seq_lens)
+            h = layer(h, seq_lens, cu_seqlens, max_seqlen)
         return h
 
     def _mlm_logits(self, h):
@@ -243,27 +309,32 @@ class BertBase(nn.Module):
         return logits + self.mlm_bias.to(logits.dtype)
 
     def forward(self, ids, token_type=None, *, attention_mask=None,
-                seq_lens=None):
-        """MLM logits [B, S, vocab]; padding arguments as in encode()
-        (logits at padded positions are unspecified but finite)."""
+                seq_lens=None, cu_seqlens=None, max_seqlen=None):
+        """MLM logits [B, S, vocab] ([T, vocab] with cu_seqlens); padding
+        arguments as in encode() (logits at padded positions are
+        unspecified but finite)."""
         return self._mlm_logits(self.encode(
             ids, token_type, attention_mask=attention_mask,
-            seq_lens=seq_lens))
+            seq_lens=seq_lens, cu_seqlens=cu_seqlens,
+            max_seqlen=max_seqlen))
 
     def forward_mlm(self, ids, positions, token_type=None, *,
-                    attention_mask=None, seq_lens=None):
+                    attention_mask=None, seq_lens=None, cu_seqlens=None,
+                    max_seqlen=None):
         """MLM logits only at the masked positions (flat indices into the
         [B*S] token stream) — the vocab projection runs on ~15% of tokens
         instead of all of them, the standard pretrain-head optimization.
-        Padding arguments as in encode()."""
+        Padding arguments as in encode(); with cu_seqlens the positions
+        index the flat [T] axis."""
         h = self.encode(ids, token_type, attention_mask=attention_mask,
-                        seq_lens=seq_lens)
+                        seq_lens=seq_lens, cu_seqlens=cu_seqlens,
+                        max_seqlen=max_seqlen)
         h = h.reshape(-1, self.cfg.hidden).index_select(0, positions)
         return self._mlm_logits(h)
 
     def mlm_loss(self, ids, positions, labels, token_type=None, *,
-                 attention_mask=None, seq_lens=None, ignore_index=-100,
-                 reduction="mean"):
+                 attention_mask=None, seq_lens=None, cu_seqlens=None,
+                 max_seqlen=None, ignore_index=-100, reduction="mean"):
         """The MLM loss at the masked positions (as forward_mlm; labels
         int64 [len(positions)]) through ops.linear_cross_entropy on the
         tied embedding weight and mlm_bias: on bf16 GPU tensors the
@@ -272,7 +343,8 @@ class BertBase(nn.Module):
         ``cross_entropy(forward_mlm(...).float(), labels)``."""
         from sparkdl.ops import functional as F_
         h = self.encode(ids, token_type, attention_mask=attention_mask,
-                        seq_lens=seq_lens)
+                        seq_lens=seq_lens, cu_seqlens=cu_seqlens,
+                        max_seqlen=max_seqlen)
         h = h.reshape(-1, self.cfg.hidden).index_select(0, positions)
         h = self.mlm_ln(torch.nn.functional.gelu(self.mlm_dense(h)))
         return F_.linear_cross_entropy(
@@ -281,7 +353,7 @@ class BertBase(nn.Module):
 
 
 def bert_pretrain_step(model, opt, batch, seq, device, use_cuda,
-                       mask_frac=0.15, seq_lens=None):
+                       mask_frac=0.15, seq_lens=None, unpad=False):
     """Build a closure running one synthetic MLM pretrain step.
 
     The vocab projection + loss run only on the masked positions
@@ -291,6 +363,11 @@ def bert_pretrain_step(model, opt, batch, seq, device, use_cuda,
     to ``seq`` with these valid lengths — MLM positions are drawn only
     among valid tokens and the lengths go to the model (device-side,
     no per-step host sync).
+
+    unpad=True (with seq_lens): pack ids, MLM positions and labels once
+    here, at set-up, and run the model on the unpadded ``[T]`` token
+    stream with ``cu_seqlens`` and no spare capacity: the same tokens,
+    positions and labels as unpad=False, without the padding's work.
     """
     cfg = model.cfg
     g = torch.Generator(device="cpu").manual_seed(7)
@@ -307,6 +384,17 @@ def bert_pretrain_step(model, opt, batch, seq, device, use_cuda,
         lens_dev = lens.to(device=device, dtype=torch.int32)
     positions = mask.flatten().nonzero(as_tuple=False).flatten().to(device)
     labels = ids.flatten().index_select(0, positions)
+    kw = {"seq_lens": lens_dev}
+    if unpad:
+        if seq_lens is None:
+            raise ValueError("unpad=True needs seq_lens")
+        from sparkdl.ops.functional import unpad_batch
+        ids, cu, index, _ = unpad_batch(ids, lens_dev)
+        # flat [B*S] position -> its place in the packed stream
+        where = torch.zeros(batch * seq, dtype=torch.long, device=device)
+        where[index] = torch.arange(index.numel(), device=device)
+        positions = where.index_select(0, positions)
+        kw = {"cu_seqlens": cu, "max_seqlen": seq}
     autocast_dev = "cuda" if use_cuda else "cpu"
     # Pure-bf16 weights (convert_bf16_training) need no autocast: every
     # GEMM already sees bf16 operands and grads flow in bf16.
@@ -319,17 +407,14 @@ def bert_pretrain_step(model, opt, batch, seq, device, use_cuda,
         if fused_mlm_loss:
             with torch.autocast(autocast_dev, dtype=torch.bfloat16,
                                 enabled=not pure_bf16):
-                loss = model.mlm_loss(ids, positions, labels,
-                                      seq_lens=lens_dev)
+                loss = model.mlm_loss(ids, positions, labels, **kw)
         elif pure_bf16:
-            logits = model.forward_mlm(ids, positions,
-                                       seq_lens=lens_dev)
+            logits = model.forward_mlm(ids, positions, **kw)
             loss = torch.nn.functional.cross_entropy(
                 logits.float(), labels)
         else:
             with torch.autocast(autocast_dev, dtype=torch.bfloat16):
-                logits = model.forward_mlm(ids, positions,
-                                           seq_lens=lens_dev)
+                logits = model.forward_mlm(ids, positions, **kw)
                 loss = torch.nn.functional.cross_entropy(
                     logits.float(), labels)
         loss.backward()

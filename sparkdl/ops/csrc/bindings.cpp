@@ -1043,6 +1043,94 @@ at::Tensor attn_bwd_packed(const at::Tensor& qkv, const at::Tensor& dO,
   return dqkv;
 }
 
+// Unpadded attention (attention_unpad.hip): the checks shared by forward
+// and backward, and the tile schedule built from cu_seqlens on the device.
+static at::Tensor attn_unpad_schedule(const at::Tensor& qkv,
+                                      const at::Tensor& cu_seqlens,
+                                      const char* who) {
+  CHECK_BF16_CUDA(qkv);
+  TORCH_CHECK(qkv.dim() == 4 && qkv.size(1) == 3 &&
+                  attn_width_ok(qkv.size(3)) && qkv.is_contiguous(),
+              who, " expects contiguous [T,3,H,64] or [T,3,H,128] bf16");
+  TORCH_CHECK(qkv.size(0) >= 1, who, " expects at least one token");
+  TORCH_CHECK(qkv.size(0) < (int64_t(1) << 31) /
+                                (3 * qkv.size(2) * qkv.size(3)),
+              who, ": T * 3 * H * D must stay below 2^31");
+  TORCH_CHECK(cu_seqlens.is_cuda() && cu_seqlens.device() == qkv.device(),
+              "cu_seqlens must be on the same GPU as the data");
+  TORCH_CHECK(cu_seqlens.scalar_type() == at::kInt,
+              "cu_seqlens must be int32");
+  TORCH_CHECK(cu_seqlens.dim() == 1 && cu_seqlens.numel() >= 2 &&
+                  cu_seqlens.is_contiguous(),
+              "cu_seqlens must be one-dimensional [B+1], B >= 1");
+  const int T = (int)qkv.size(0), B = (int)cu_seqlens.numel() - 1;
+  DeviceGuard guard(qkv.device());
+  auto sched = at::empty({1 + attn_unpad_max_tiles(T, B), 4},
+                         cu_seqlens.options());
+  launch_attn_unpad_schedule(cu_seqlens.data_ptr<int>(), B, T,
+                             sched.data_ptr<int>(), cur_stream());
+  return sched;
+}
+
+std::vector<at::Tensor> attn_fwd_unpad(
+    const at::Tensor& qkv, const at::Tensor& cu_seqlens, int64_t max_seqlen,
+    double dropout_p, const c10::optional<at::Tensor>& seed, bool causal) {
+  auto sched = attn_unpad_schedule(qkv, cu_seqlens, "attn_fwd_unpad");
+  TORCH_CHECK(max_seqlen >= 1 && max_seqlen < (int64_t(1) << 31),
+              "max_seqlen out of range");
+  TORCH_CHECK(dropout_p == 0.0 || seed.has_value(),
+              "dropout needs a seed tensor");
+  const int T = (int)qkv.size(0), H = (int)qkv.size(2),
+            D = (int)qkv.size(3), B = (int)cu_seqlens.numel() - 1;
+  DeviceGuard guard(qkv.device());
+  auto O = at::empty({T, H * D}, qkv.options());
+  auto LSE = at::empty({H, T}, qkv.options().dtype(at::kFloat));
+  launch_attn_unpad_fwd(bf_ptr(qkv), bf_ptr_mut(O), LSE.data_ptr<float>(),
+                        seed_ptr(seed), sched.data_ptr<int>(), B, T, H, D,
+                        (int)max_seqlen, (float)dropout_p, causal,
+                        cur_stream());
+  return {O, LSE};
+}
+
+at::Tensor attn_bwd_unpad(const at::Tensor& qkv, const at::Tensor& dO,
+                          const at::Tensor& O, const at::Tensor& LSE,
+                          const at::Tensor& cu_seqlens, int64_t max_seqlen,
+                          double dropout_p,
+                          const c10::optional<at::Tensor>& seed,
+                          bool causal) {
+  auto sched = attn_unpad_schedule(qkv, cu_seqlens, "attn_bwd_unpad");
+  CHECK_BF16_CUDA(dO);
+  CHECK_BF16_CUDA(O);
+  CHECK_F32_CUDA(LSE);
+  const int T = (int)qkv.size(0), H = (int)qkv.size(2),
+            D = (int)qkv.size(3), B = (int)cu_seqlens.numel() - 1;
+  TORCH_CHECK(dO.dim() == 2 && dO.size(0) == T &&
+                  dO.size(1) == (int64_t)H * D && dO.is_contiguous() &&
+                  O.sizes() == dO.sizes() && O.is_contiguous(),
+              "attn_bwd_unpad expects contiguous dO and O [T, H*D]");
+  TORCH_CHECK(LSE.dim() == 2 && LSE.size(0) == H && LSE.size(1) == T &&
+                  LSE.is_contiguous(),
+              "attn_bwd_unpad expects contiguous [H, T] fp32 LSE");
+  TORCH_CHECK(dO.device() == qkv.device() && O.device() == qkv.device() &&
+                  LSE.device() == qkv.device(),
+              "attn_bwd_unpad: all tensors on one device");
+  TORCH_CHECK(max_seqlen >= 1 && max_seqlen < (int64_t(1) << 31),
+              "max_seqlen out of range");
+  TORCH_CHECK(dropout_p == 0.0 || seed.has_value(),
+              "dropout needs a seed tensor");
+  DeviceGuard guard(qkv.device());
+  auto dqkv = at::empty_like(qkv);
+  auto Drow = at::empty_like(LSE);
+  launch_attn_unpad_rowdot(bf_ptr(dO), bf_ptr(O), Drow.data_ptr<float>(), T,
+                           H, D, cur_stream());
+  launch_attn_unpad_bwd(bf_ptr(qkv), bf_ptr(dO), LSE.data_ptr<float>(),
+                        Drow.data_ptr<float>(), bf_ptr_mut(dqkv),
+                        seed_ptr(seed), sched.data_ptr<int>(), B, T, H, D,
+                        (int)max_seqlen, (float)dropout_p, causal,
+                        cur_stream());
+  return dqkv;
+}
+
 at::Tensor wgrad_splitk(const at::Tensor& dZ, const at::Tensor& X) {
   CHECK_BF16_CUDA(dZ);
   CHECK_BF16_CUDA(X);
@@ -1289,6 +1377,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dO"), py::arg("lse"), py::arg("drow"),
         py::arg("dropout_p"), py::arg("seed"),
         py::arg("seqlens") = py::none(), py::arg("causal") = false);
+  m.def("attn_fwd_unpad", &attn_fwd_unpad,
+        "Flash attention fwd over unpadded [T,3,H,D] qkv -> (O, LSE)",
+        py::arg("qkv"), py::arg("cu_seqlens"), py::arg("max_seqlen"),
+        py::arg("dropout_p"), py::arg("seed"), py::arg("causal"));
+  m.def("attn_bwd_unpad", &attn_bwd_unpad,
+        "Flash attention bwd over unpadded qkv -> dqkv", py::arg("qkv"),
+        py::arg("dO"), py::arg("o"), py::arg("lse"), py::arg("cu_seqlens"),
+        py::arg("max_seqlen"), py::arg("dropout_p"), py::arg("seed"),
+        py::arg("causal"));
   m.def("gbt_histogram", &gbt_histogram, "GBT g/h histogram (N7)");
   m.def("bn_fwd", &bn_fwd, "Fused BatchNorm(+add)(+ReLU) fwd (bf16 NHWC)");
   m.def("bn_bwd", &bn_bwd, "Fused BatchNorm(+add)(+ReLU) bwd (bf16 NHWC)");

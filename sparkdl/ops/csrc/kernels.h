@@ -332,6 +332,32 @@ void launch_attn_d128_bwd(const short* Q, const short* K, const short* V,
                           const int* seqlens, bool causal,
                           hipStream_t stream);
 
+// Flash attention over an unpadded token buffer (attention_unpad.hip):
+// qkv [T, 3, H, D] bf16 with the sequences back to back, D = 64 or 128,
+// cu_seqlens DEVICE int32 [B+1] (sequence b = tokens cu[b] .. cu[b+1]-1,
+// tokens from cu[B] on are spare capacity and come back zero); O and dO
+// [T, H*D], LSE and Drow [H, T] fp32, dqkv shaped as qkv. `sched` is
+// 4 * (1 + attn_unpad_max_tiles(T, B)) ints of device workspace that
+// launch_attn_unpad_schedule fills from cu_seqlens in the same stream
+// before a forward or a backward launch reads it. Dropout hashes
+// (seed, b*H + h, local q, local k, max_seqlen): the mask of the padded
+// kernels at S = max_seqlen. T >= 1.
+int attn_unpad_max_tiles(int T, int B);
+void launch_attn_unpad_schedule(const int* cu_seqlens, int B, int T,
+                                int* sched, hipStream_t stream);
+void launch_attn_unpad_fwd(const short* qkv, short* O, float* LSE,
+                           const long long* seed, const int* sched, int B,
+                           int T, int H, int D, int max_seqlen,
+                           float dropout_p, bool causal, hipStream_t stream);
+// Drow[h][t] = sum_d dO[t][h*D + d] * O[t][h*D + d]
+void launch_attn_unpad_rowdot(const short* dO, const short* O, float* Drow,
+                              int T, int H, int D, hipStream_t stream);
+void launch_attn_unpad_bwd(const short* qkv, const short* dO,
+                           const float* LSE, const float* Drow, short* dqkv,
+                           const long long* seed, const int* sched, int B,
+                           int T, int H, int D, int max_seqlen,
+                           float dropout_p, bool causal, hipStream_t stream);
+
 // GBT per-(node,feature,bin) gradient/hessian histograms
 // (SURVEY.md §2.2 N7). bmap: per-block {node, f0, start, count} over a
 // node-sorted row_list; hist: fp32 [n_nodes, F, 256, 2], pre-zeroed.

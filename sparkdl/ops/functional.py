@@ -663,6 +663,124 @@ def flash_attention_packed(qkv, dropout_p=0.0, seq_lens=None,
                                     causal)
 
 
+# ---------------------------------------------------------------------------
+# Unpadded (cu_seqlens) attention: the sequences of a batch back to back
+# in one [T, ...] token buffer, no padding between them
+# (csrc/attention_unpad.hip).
+# ---------------------------------------------------------------------------
+
+def unpadded_attention_ref(qkv, cu_seqlens, dropout_p=0.0, causal=False):
+    """Plain PyTorch attention over a packed batch: qkv ``[T, 3, H, D]``,
+    cu_seqlens integer ``[B+1]`` (sequence b is the tokens
+    ``cu[b] .. cu[b+1]-1``) -> O ``[T, H*D]`` in qkv's dtype. Every
+    sequence goes through the arithmetic of masked_attention_ref on its
+    own; tokens at or beyond ``cu[B]`` (spare capacity) give zeros and
+    get no gradient. Reads cu_seqlens back to the host: it SYNCS, and is
+    the CPU path, the fallback for shapes without kernels and the tests'
+    oracle, not a hot path."""
+    T, _, H, D = qkv.shape
+    cu = [min(max(int(c), 0), T) for c in cu_seqlens.tolist()]
+    out = []
+    for s, e in zip(cu[:-1], cu[1:]):
+        if e > s:
+            q, k, v = qkv[s:e].permute(1, 2, 0, 3).unsqueeze(1).unbind(0)
+            o = masked_attention_ref(q, k, v, None, dropout_p, causal)
+            out.append(o[0].transpose(0, 1).reshape(e - s, H * D))
+    out.append(qkv.new_zeros(T - cu[-1], H * D))
+    return torch.cat(out)
+
+
+class _FlashAttnUnpaddedFn(torch.autograd.Function):
+    """Attention over the unpadded qkv buffer [T,3,H,D] (the qkv Linear's
+    output on a [T, hidden] token matrix, viewed) -> O [T, H*D]; the
+    backward emits dqkv in the same layout. cu_seqlens gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, qkv, cu_seqlens, max_seqlen, dropout_p, causal):
+        C = _ops.ext()
+        seed = None
+        if dropout_p > 0:
+            seed = _attn_seed_tensor(qkv.device)
+            seed.add_(1)
+            # the backward replays this step's seed
+            seed = seed.clone()
+        o, lse = C.attn_fwd_unpad(qkv, cu_seqlens, int(max_seqlen),
+                                  float(dropout_p), seed, bool(causal))
+        ctx.save_for_backward(qkv, o, lse,
+                              seed if seed is not None else
+                              torch.empty(0), cu_seqlens)
+        ctx.args = (int(max_seqlen), float(dropout_p), bool(causal))
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        C = _ops.ext()
+        qkv, o, lse, seed, cu_seqlens = ctx.saved_tensors
+        if seed.numel() == 0:
+            seed = None
+        max_seqlen, dropout_p, causal = ctx.args
+        # D_i = rowsum(dO o O) is a kernel of its own inside the call
+        dqkv = C.attn_bwd_unpad(qkv, do.contiguous(), o, lse, cu_seqlens,
+                                max_seqlen, dropout_p, seed, causal)
+        return dqkv, None, None, None, None
+
+
+def flash_attention_unpadded_ok(qkv):
+    return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 4
+            and qkv.shape[1] == 3 and qkv.shape[3] in (64, 128)
+            and qkv.shape[0] > 0)
+
+
+def flash_attention_unpadded(qkv, cu_seqlens, max_seqlen, dropout_p=0.0,
+                             causal=False):
+    """qkv: [T, 3, H, D] bf16, D = 64 or 128, the sequences of a batch
+    back to back -> O [T, H*D]; the caller checks
+    flash_attention_unpadded_ok first.
+
+    cu_seqlens: int32 [B+1] on qkv's device, non-decreasing, cu[0] = 0,
+    cu[B] <= T. Sequence b is the tokens cu[b] .. cu[b+1]-1 and attends
+    to itself alone (causal=True: key k from query q iff k <= q, local
+    positions); it may be empty and may start at any token. Tokens from
+    cu[B] on are spare capacity: O and dqkv are exactly zero there. No
+    token is computed or stored for padding, so the cost is that of the
+    real tokens. The lengths are read on the device only: no host sync,
+    graph-capturable, and cu_seqlens may be refilled in place between
+    replays of a graph over a fixed-capacity buffer.
+
+    max_seqlen: a host integer >= every length, used for nothing but the
+    dropout hash: with the same seed the mask of sequence b is the one
+    flash_attention_packed draws for row b of the same batch right-padded
+    to S = max_seqlen."""
+    return _FlashAttnUnpaddedFn.apply(qkv.contiguous(), cu_seqlens,
+                                      max_seqlen, dropout_p, causal)
+
+
+def unpad_batch(x, seq_lens):
+    """Gather the valid tokens of a right-padded batch: x ``[B, S, ...]``
+    (ids or hidden states), seq_lens integer ``[B]`` (clamped into
+    ``[0, S]``) -> ``(packed [T, ...], cu_seqlens int32 [B+1], index
+    int64 [T], max_seqlen)``. ``index`` holds the tokens' flat positions
+    in ``[B*S]``, for pad_batch and for packing labels or positions the
+    same way; ``max_seqlen`` is ``S``. Learning T SYNCS once; a caller
+    that keeps its data packed never needs this."""
+    B, S = x.shape[:2]
+    lens = torch.as_tensor(seq_lens, device=x.device).long().clamp(0, S)
+    valid = torch.arange(S, device=x.device) < lens.unsqueeze(1)
+    index = valid.flatten().nonzero().flatten()
+    cu = torch.zeros(B + 1, dtype=torch.int32, device=x.device)
+    cu[1:] = lens.cumsum(0)
+    packed = x.reshape((B * S,) + x.shape[2:]).index_select(0, index)
+    return packed, cu, index, S
+
+
+def pad_batch(packed, index, B, S):
+    """Scatter ``packed [>= len(index), ...]`` back to ``[B, S, ...]`` at
+    the flat positions ``index`` of unpad_batch; padding is zero."""
+    out = packed.new_zeros((B * S,) + packed.shape[1:])
+    out = out.index_copy(0, index, packed[:index.numel()])
+    return out.view((B, S) + packed.shape[1:])
+
+
 def _conv_gemm(a2d, w):
     """Best-kernel cascade for bias-free GEMMs (1x1 conv fwd/dgrad):
     streaming tall-skinny kernel when the shape fits, else the 256x256
