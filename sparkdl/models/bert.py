@@ -40,6 +40,18 @@ profiles/README.md, "Flash attention, 128-wide heads"); a call with
 ``seq_lens`` always does: its only alternative is the composed
 reference, which materialises the [B,h,S,S] fp32 scores.
 
+``BertConfig(kv_heads=k)`` with k < heads is grouped-query attention:
+the ``heads`` query heads share k key/value heads in groups of
+``heads // k`` and ``qkv`` projects to ``hidden + 2*k*head_dim``
+features, laid out [Q heads | K heads | V heads]. On the padded path,
+at width 128 in bf16 on the GPU with ``S % 64 == 0``, attention is
+``ops.flash_attention_gqa_packed`` (K/V heads read in place, dK/dV
+summed per group in the kernel): always with ``seq_lens``, and without
+them when SPARKDL_FLASH_GQA is "1" (see ``_FLASH_GQA_DEFAULT``).
+Everywhere else, the unpadded path included, K and V are expanded to
+``heads`` heads in front of what the multi-head model calls.
+``kv_heads=None`` or ``== heads`` is the multi-head model, unchanged.
+
 Unpadded batches: ``encode``, ``forward``, ``forward_mlm`` and
 ``mlm_loss`` take ``cu_seqlens`` (int32 ``[B+1]``, with ``max_seqlen``
 defaulting to ``cfg.max_seq``). ``ids`` and ``token_type`` are then
@@ -64,7 +76,8 @@ from sparkdl.ops import LayerNorm, Linear, LinearGelu
 class BertConfig:
     def __init__(self, vocab_size=30522, hidden=768, layers=12, heads=12,
                  ffn=3072, max_seq=512, type_vocab=2, dropout=0.1,
-                 fused_dropout_ln=None, fused_mlm_loss=None, causal=False):
+                 fused_dropout_ln=None, fused_mlm_loss=None, causal=False,
+                 kv_heads=None):
         self.vocab_size = vocab_size
         self.hidden = hidden
         self.layers = layers
@@ -85,6 +98,14 @@ class BertConfig:
         self.fused_mlm_loss = bool(fused_mlm_loss)
         # left-to-right (decoder-style) self-attention
         self.causal = bool(causal)
+        # grouped-query attention: `heads` query heads share `kv_heads`
+        # key/value heads (None or == heads: plain multi-head attention)
+        if kv_heads is None:
+            kv_heads = heads
+        if kv_heads < 1 or heads % kv_heads:
+            raise ValueError("kv_heads=%r must divide heads=%r"
+                             % (kv_heads, heads))
+        self.kv_heads = int(kv_heads)
 
 
 class BertEmbeddings(nn.Module):
@@ -119,6 +140,13 @@ class BertEmbeddings(nn.Module):
 # profiles/attn_d128.log against scaled_dot_product_attention).
 _FLASH_D128_DEFAULT = "0"
 
+# Value of SPARKDL_FLASH_GQA when it is unset: whether a kv_heads model
+# takes the grouped-query kernels without seq_lens (decided by the
+# measurement in profiles/attn_gqa.log against K/V expanded to every
+# query head in front of the 128-wide kernels and of
+# scaled_dot_product_attention). With seq_lens it always does.
+_FLASH_GQA_DEFAULT = "0"
+
 
 class BertSelfAttention(nn.Module):
     # False sends every call through the library / composed branch
@@ -128,16 +156,61 @@ class BertSelfAttention(nn.Module):
         super().__init__()
         self.heads = cfg.heads
         self.head_dim = cfg.hidden // cfg.heads
-        self.qkv = Linear(cfg.hidden, 3 * cfg.hidden)
+        self.kv_heads = getattr(cfg, "kv_heads", cfg.heads)
+        if self.kv_heads == self.heads:
+            self.qkv = Linear(cfg.hidden, 3 * cfg.hidden)
+        else:  # one projection to [Q heads | K heads | V heads]
+            self.qkv = Linear(cfg.hidden, cfg.hidden
+                              + 2 * self.kv_heads * self.head_dim)
         self.out = Linear(cfg.hidden, cfg.hidden)
         self.drop_p = cfg.dropout
         self.causal = getattr(cfg, "causal", False)
+
+    def _expanded(self, qkv):
+        """Grouped-query projection output [..., heads + 2*kv_heads, d]
+        -> q, k, v [..., heads, d], K/V heads repeated over their group
+        (what every composed branch and the unpadded kernels take)."""
+        h, hkv = self.heads, self.kv_heads
+        q, k, v = qkv.split([h, hkv, hkv], dim=-2)
+        return (q, k.repeat_interleave(h // hkv, dim=-2),
+                v.repeat_interleave(h // hkv, dim=-2))
+
+    def _forward_gqa(self, x, seq_lens):
+        """The padded path with kv_heads < heads."""
+        from sparkdl.ops import functional as F_
+        B, S, H = x.shape
+        qkv = self.qkv(x).view(B, S, self.heads + 2 * self.kv_heads,
+                               self.head_dim)
+        p = self.drop_p if self.training else 0.0
+        take = seq_lens is not None or os.environ.get(
+            "SPARKDL_FLASH_GQA", _FLASH_GQA_DEFAULT) == "1"
+        if self.use_flash and take and F_.flash_attention_gqa_ok(qkv):
+            # K/V heads read in place, dK/dV summed per group in-kernel
+            o = F_.flash_attention_gqa_packed(
+                qkv, self.kv_heads, dropout_p=p, seq_lens=seq_lens,
+                causal=self.causal)
+        else:
+            q, k, v = (t.transpose(1, 2) for t in self._expanded(qkv))
+            if seq_lens is None:
+                o = nn.functional.scaled_dot_product_attention(
+                    q, k, v, dropout_p=p, is_causal=self.causal)
+            else:
+                o = F_.masked_attention_ref(q, k, v, seq_lens, dropout_p=p,
+                                            causal=self.causal)
+            o = o.transpose(1, 2).reshape(B, S, H)
+        return self.out(o)
 
     def _forward_unpadded(self, x, cu_seqlens, max_seqlen):
         """x [T, hidden], the sequences back to back (cu_seqlens int32
         [B+1]); the attention output at spare tokens is exactly zero."""
         from sparkdl.ops import functional as F_
-        qkv = self.qkv(x).view(x.shape[0], 3, self.heads, self.head_dim)
+        if self.kv_heads != self.heads:
+            # no grouped-query variant of the unpadded kernels: expand
+            qkv = torch.stack(self._expanded(self.qkv(x).view(
+                x.shape[0], -1, self.head_dim)), dim=1)
+        else:
+            qkv = self.qkv(x).view(x.shape[0], 3, self.heads,
+                                   self.head_dim)
         p = self.drop_p if self.training else 0.0
         if self.use_flash and F_.flash_attention_unpadded_ok(qkv):
             # no S % 64 condition and no opt-in at width 128: the only
@@ -157,6 +230,8 @@ class BertSelfAttention(nn.Module):
         from sparkdl.ops import functional as F_
         if cu_seqlens is not None:
             return self._forward_unpadded(x, cu_seqlens, max_seqlen)
+        if self.kv_heads != self.heads:
+            return self._forward_gqa(x, seq_lens)
         B, S, H = x.shape
         qkv = self.qkv(x).view(B, S, 3, self.heads, self.head_dim)
         p = self.drop_p if self.training else 0.0

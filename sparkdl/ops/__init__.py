@@ -46,6 +46,7 @@ from sparkdl.ops.functional import (  # noqa: F401,E402
     layer_norm, bias_gelu, batch_norm_act, batch_norm_relu_maxpool,
     layer_norm_ref, bias_gelu_ref,
     flash_attention, flash_attention_packed, masked_attention_ref,
+    flash_attention_gqa_packed, flash_attention_gqa_ok,
     flash_attention_unpadded, flash_attention_unpadded_ok,
     unpadded_attention_ref, unpad_batch, pad_batch,
     seqlens_from_mask, dropout_add_layer_norm, dropout_keep_mask,

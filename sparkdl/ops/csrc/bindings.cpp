@@ -1043,6 +1043,165 @@ at::Tensor attn_bwd_packed(const at::Tensor& qkv, const at::Tensor& dO,
   return dqkv;
 }
 
+// Grouped-query attention (attention_gqa.hip), 128-wide heads. Every
+// extent the kernels index with is checked here, before any launch.
+static void attn_gqa_check_heads(int64_t Hq, int64_t Hkv, int64_t S,
+                                 int64_t B, const char* who) {
+  TORCH_CHECK(Hq >= 1 && Hkv >= 1 && Hq % Hkv == 0, who, ": Hkv = ", Hkv,
+              " must divide Hq = ", Hq);
+  TORCH_CHECK(S >= 64 && S % 64 == 0 && S / 64 <= 65535, who,
+              " requires S % 64 == 0, 64 <= S <= 65535 * 64, got ", S);
+  TORCH_CHECK(B >= 1 && B * Hq < (int64_t(1) << 31) / S, who,
+              ": B * Hq * S must stay below 2^31");
+}
+
+// q/dO [B*Hq,S,128], k/v [B*Hkv,S,128] -> B
+static int attn_gqa_check_qkv(const at::Tensor& Q, const at::Tensor& K,
+                              const at::Tensor& V, int64_t Hq, int64_t Hkv,
+                              const char* who) {
+  CHECK_BF16_CUDA(Q);
+  CHECK_BF16_CUDA(K);
+  CHECK_BF16_CUDA(V);
+  TORCH_CHECK(Q.dim() == 3 && K.dim() == 3 && Q.size(2) == 128 &&
+                  K.size(2) == 128 && K.sizes() == V.sizes() &&
+                  Q.size(1) == K.size(1),
+              who, " expects bf16 q [B*Hq, S, 128] and k, v [B*Hkv, S, 128]");
+  TORCH_CHECK(K.device() == Q.device() && V.device() == Q.device(), who,
+              ": all tensors on one device");
+  TORCH_CHECK(Hq >= 1 && Hkv >= 1 && Q.size(0) % Hq == 0 &&
+                  K.size(0) == Q.size(0) / Hq * Hkv,
+              who, ": q holds ", Q.size(0), " heads and k ", K.size(0),
+              ", not B*", Hq, " and B*", Hkv);
+  attn_gqa_check_heads(Hq, Hkv, Q.size(1), Q.size(0) / Hq, who);
+  return (int)(Q.size(0) / Hq);
+}
+
+static void attn_gqa_check_bwd(const at::Tensor& LSE, const at::Tensor& Drow,
+                               const at::Tensor& like, int64_t BHq,
+                               int64_t S, const char* who) {
+  CHECK_F32_CUDA(LSE);
+  CHECK_F32_CUDA(Drow);
+  TORCH_CHECK(LSE.dim() == 2 && LSE.size(0) == BHq && LSE.size(1) == S &&
+                  LSE.sizes() == Drow.sizes(),
+              who, " expects [B*Hq, S] fp32 LSE and Drow");
+  TORCH_CHECK(LSE.device() == like.device() &&
+                  Drow.device() == like.device(),
+              who, ": all tensors on one device");
+}
+
+std::vector<at::Tensor> attn_gqa_fwd(
+    const at::Tensor& Q, const at::Tensor& K, const at::Tensor& V,
+    double dropout_p, const c10::optional<at::Tensor>& seed,
+    const c10::optional<at::Tensor>& seqlens, bool causal, int64_t Hq,
+    int64_t Hkv) {
+  const int B = attn_gqa_check_qkv(Q, K, V, Hq, Hkv, "attn_gqa_fwd");
+  const int S = (int)Q.size(1);
+  TORCH_CHECK(dropout_p == 0.0 || seed.has_value(),
+              "dropout needs a seed tensor");
+  const int* lens = seqlens_ptr(seqlens, Q, B);
+  DeviceGuard guard(Q.device());
+  auto O = at::empty_like(Q);
+  auto LSE = at::empty({Q.size(0), S}, Q.options().dtype(at::kFloat));
+  launch_attn_gqa_fwd(bf_ptr(Q), bf_ptr(K), bf_ptr(V), bf_ptr_mut(O),
+                      LSE.data_ptr<float>(), seed_ptr(seed), B, S, (int)Hq,
+                      (int)Hkv, false, (float)dropout_p, lens, causal,
+                      cur_stream());
+  return {O, LSE};
+}
+
+std::vector<at::Tensor> attn_gqa_bwd(
+    const at::Tensor& Q, const at::Tensor& K, const at::Tensor& V,
+    const at::Tensor& dO, const at::Tensor& LSE, const at::Tensor& Drow,
+    double dropout_p, const c10::optional<at::Tensor>& seed,
+    const c10::optional<at::Tensor>& seqlens, bool causal, int64_t Hq,
+    int64_t Hkv) {
+  const int B = attn_gqa_check_qkv(Q, K, V, Hq, Hkv, "attn_gqa_bwd");
+  const int S = (int)Q.size(1);
+  CHECK_BF16_CUDA(dO);
+  TORCH_CHECK(dO.sizes() == Q.sizes() && dO.device() == Q.device(),
+              "attn_gqa_bwd expects dO shaped as q, on q's device");
+  attn_gqa_check_bwd(LSE, Drow, Q, Q.size(0), S, "attn_gqa_bwd");
+  TORCH_CHECK(dropout_p == 0.0 || seed.has_value(),
+              "dropout needs a seed tensor");
+  const int* lens = seqlens_ptr(seqlens, Q, B);
+  DeviceGuard guard(Q.device());
+  auto dQ = at::empty_like(Q);
+  auto dK = at::empty_like(K);
+  auto dV = at::empty_like(V);
+  launch_attn_gqa_bwd(bf_ptr(Q), bf_ptr(K), bf_ptr(V), bf_ptr(dO),
+                      LSE.data_ptr<float>(), Drow.data_ptr<float>(),
+                      bf_ptr_mut(dQ), bf_ptr_mut(dK), bf_ptr_mut(dV),
+                      seed_ptr(seed), B, S, (int)Hq, (int)Hkv, false,
+                      (float)dropout_p, lens, causal, cur_stream());
+  return {dQ, dK, dV};
+}
+
+// qkv [B,S,Hq+2Hkv,128]: heads 0..Hq-1 are Q, then Hkv K heads, then Hkv
+// V heads (one fused projection's output)
+static void attn_gqa_check_packed(const at::Tensor& qkv, int64_t Hq,
+                                  int64_t Hkv, const char* who) {
+  CHECK_BF16_CUDA(qkv);
+  TORCH_CHECK(qkv.dim() == 4 && qkv.size(3) == 128, who,
+              " expects contiguous [B, S, Hq + 2*Hkv, 128] bf16");
+  TORCH_CHECK(Hq >= 1 && Hkv >= 1 && qkv.size(2) == Hq + 2 * Hkv, who,
+              ": qkv holds ", qkv.size(2), " heads, not ", Hq, " + 2*", Hkv);
+  attn_gqa_check_heads(Hq, Hkv, qkv.size(1), qkv.size(0), who);
+  TORCH_CHECK(qkv.size(0) < (int64_t(1) << 31) / (qkv.size(1) * qkv.size(2)),
+              who, ": B * S * (Hq + 2*Hkv) must stay below 2^31");
+}
+
+std::vector<at::Tensor> attn_gqa_fwd_packed(
+    const at::Tensor& qkv, double dropout_p,
+    const c10::optional<at::Tensor>& seed,
+    const c10::optional<at::Tensor>& seqlens, bool causal, int64_t Hq,
+    int64_t Hkv) {
+  attn_gqa_check_packed(qkv, Hq, Hkv, "attn_gqa_fwd_packed");
+  const int B = (int)qkv.size(0), S = (int)qkv.size(1);
+  TORCH_CHECK(dropout_p == 0.0 || seed.has_value(),
+              "dropout needs a seed tensor");
+  const int* lens = seqlens_ptr(seqlens, qkv, B);
+  DeviceGuard guard(qkv.device());
+  auto O = at::empty({B, S, Hq * 128}, qkv.options());
+  auto LSE = at::empty({B * Hq, S}, qkv.options().dtype(at::kFloat));
+  const short* base = bf_ptr(qkv);
+  launch_attn_gqa_fwd(base, base + Hq * 128, base + (Hq + Hkv) * 128,
+                      bf_ptr_mut(O), LSE.data_ptr<float>(), seed_ptr(seed),
+                      B, S, (int)Hq, (int)Hkv, true, (float)dropout_p, lens,
+                      causal, cur_stream());
+  return {O, LSE};
+}
+
+at::Tensor attn_gqa_bwd_packed(const at::Tensor& qkv, const at::Tensor& dO,
+                               const at::Tensor& LSE, const at::Tensor& Drow,
+                               double dropout_p,
+                               const c10::optional<at::Tensor>& seed,
+                               const c10::optional<at::Tensor>& seqlens,
+                               bool causal, int64_t Hq, int64_t Hkv) {
+  attn_gqa_check_packed(qkv, Hq, Hkv, "attn_gqa_bwd_packed");
+  const int B = (int)qkv.size(0), S = (int)qkv.size(1);
+  CHECK_BF16_CUDA(dO);
+  TORCH_CHECK(dO.dim() == 3 && dO.size(0) == B && dO.size(1) == S &&
+                  dO.size(2) == Hq * 128 && dO.device() == qkv.device(),
+              "attn_gqa_bwd_packed expects dO [B, S, Hq*128] on qkv's "
+              "device");
+  attn_gqa_check_bwd(LSE, Drow, qkv, (int64_t)B * Hq, S,
+                     "attn_gqa_bwd_packed");
+  TORCH_CHECK(dropout_p == 0.0 || seed.has_value(),
+              "dropout needs a seed tensor");
+  const int* lens = seqlens_ptr(seqlens, qkv, B);
+  DeviceGuard guard(qkv.device());
+  auto dqkv = at::empty_like(qkv);
+  const short* base = bf_ptr(qkv);
+  short* gbase = bf_ptr_mut(dqkv);
+  launch_attn_gqa_bwd(base, base + Hq * 128, base + (Hq + Hkv) * 128,
+                      bf_ptr(dO), LSE.data_ptr<float>(),
+                      Drow.data_ptr<float>(), gbase, gbase + Hq * 128,
+                      gbase + (Hq + Hkv) * 128, seed_ptr(seed), B, S,
+                      (int)Hq, (int)Hkv, true, (float)dropout_p, lens,
+                      causal, cur_stream());
+  return dqkv;
+}
+
 // Unpadded attention (attention_unpad.hip): the checks shared by forward
 // and backward, and the tile schedule built from cu_seqlens on the device.
 static at::Tensor attn_unpad_schedule(const at::Tensor& qkv,
@@ -1377,6 +1536,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dO"), py::arg("lse"), py::arg("drow"),
         py::arg("dropout_p"), py::arg("seed"),
         py::arg("seqlens") = py::none(), py::arg("causal") = false);
+  m.def("attn_gqa_fwd", &attn_gqa_fwd,
+        "Grouped-query flash attention fwd (D=128): q [B*Hq,S,128], "
+        "k/v [B*Hkv,S,128] -> (O, LSE)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dropout_p"),
+        py::arg("seed"), py::arg("seqlens"), py::arg("causal"),
+        py::arg("num_q_heads"), py::arg("num_kv_heads"));
+  m.def("attn_gqa_bwd", &attn_gqa_bwd,
+        "Grouped-query flash attention bwd -> (dQ, dK, dV)", py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("dO"), py::arg("lse"),
+        py::arg("drow"), py::arg("dropout_p"), py::arg("seed"),
+        py::arg("seqlens"), py::arg("causal"), py::arg("num_q_heads"),
+        py::arg("num_kv_heads"));
+  m.def("attn_gqa_fwd_packed", &attn_gqa_fwd_packed,
+        "Grouped-query flash attention fwd over [B,S,Hq+2Hkv,128]",
+        py::arg("qkv"), py::arg("dropout_p"), py::arg("seed"),
+        py::arg("seqlens"), py::arg("causal"), py::arg("num_q_heads"),
+        py::arg("num_kv_heads"));
+  m.def("attn_gqa_bwd_packed", &attn_gqa_bwd_packed,
+        "Grouped-query flash attention bwd -> packed dqkv", py::arg("qkv"),
+        py::arg("dO"), py::arg("lse"), py::arg("drow"),
+        py::arg("dropout_p"), py::arg("seed"), py::arg("seqlens"),
+        py::arg("causal"), py::arg("num_q_heads"),
+        py::arg("num_kv_heads"));
   m.def("attn_fwd_unpad", &attn_fwd_unpad,
         "Flash attention fwd over unpadded [T,3,H,D] qkv -> (O, LSE)",
         py::arg("qkv"), py::arg("cu_seqlens"), py::arg("max_seqlen"),

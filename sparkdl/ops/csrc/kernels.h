@@ -332,6 +332,29 @@ void launch_attn_d128_bwd(const short* Q, const short* K, const short* V,
                           const int* seqlens, bool causal,
                           hipStream_t stream);
 
+// Grouped-query flash attention, D=128 heads (attention_gqa.hip): Hq
+// query heads share Hkv key/value heads (Hq % Hkv == 0; query head hq
+// reads K/V head hq / (Hq/Hkv)), which are read in place, never
+// expanded. packed: Q, K and V point at heads 0, Hq and Hq+Hkv of one
+// contiguous [B,S,Hq+2Hkv,128] buffer, O/dO are [B,S,Hq*128] and dQ, dK,
+// dV point into a gradient buffer laid out as the input. Otherwise Q, O,
+// dO, dQ are contiguous [B*Hq,S,128] and K, V, dK, dV [B*Hkv,S,128].
+// LSE and Drow are [B*Hq,S] fp32; seqlens (nullable, DEVICE int32) holds
+// B entries; dropout hashes (seed, b*Hq + hq, q*S + k). dK/dV sum each
+// group in registers and are written once: no atomics, no scratch.
+void launch_attn_gqa_fwd(const short* Q, const short* K, const short* V,
+                         short* O, float* LSE, const long long* seed, int B,
+                         int S, int Hq, int Hkv, bool packed,
+                         float dropout_p, const int* seqlens, bool causal,
+                         hipStream_t stream);
+void launch_attn_gqa_bwd(const short* Q, const short* K, const short* V,
+                         const short* dO, const float* LSE,
+                         const float* Drow, short* dQ, short* dK, short* dV,
+                         const long long* seed, int B, int S, int Hq,
+                         int Hkv, bool packed, float dropout_p,
+                         const int* seqlens, bool causal,
+                         hipStream_t stream);
+
 // Flash attention over an unpadded token buffer (attention_unpad.hip):
 // qkv [T, 3, H, D] bf16 with the sequences back to back, D = 64 or 128,
 // cu_seqlens DEVICE int32 [B+1] (sequence b = tokens cu[b] .. cu[b+1]-1,

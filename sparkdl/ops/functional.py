@@ -581,8 +581,16 @@ def flash_attention(q, k, v, dropout_p=0.0, seq_lens=None, causal=False):
 
     causal=True: query q attends to keys k <= q only (self-attention,
     and k < len with seq_lens), through kernels that never stage the
-    tiles above the diagonal."""
+    tiles above the diagonal.
+
+    Grouped-query attention: k and v may hold fewer heads than q,
+    ``[B, Hkv, S, 128]`` with Hkv dividing h (d = 128 only). Query head
+    i then attends to K/V head ``i // (h // Hkv)``; the shared heads
+    are read in place (csrc/attention_gqa.hip) and dk/dv come back as
+    ``[B, Hkv, S, 128]``, each group summed inside the kernel."""
     B, h, S, d = q.shape
+    if k.shape[1] != h:
+        return _flash_attention_gqa(q, k, v, dropout_p, seq_lens, causal)
     q3 = q.reshape(B * h, S, d).contiguous()
     k3 = k.reshape(B * h, S, d).contiguous()
     v3 = v.reshape(B * h, S, d).contiguous()
@@ -661,6 +669,133 @@ def flash_attention_packed(qkv, dropout_p=0.0, seq_lens=None,
     tile pairs at S=512) and mask inside the diagonal tiles."""
     return _FlashAttnPackedFn.apply(qkv.contiguous(), dropout_p, seq_lens,
                                     causal)
+
+
+# ---------------------------------------------------------------------------
+# Grouped-query attention (csrc/attention_gqa.hip): Hq query heads share
+# Hkv < Hq key/value heads, 128-wide. K/V are never expanded to Hq heads
+# and dK/dV are summed over each group inside one workgroup.
+# ---------------------------------------------------------------------------
+
+class _FlashAttnGqaFn(torch.autograd.Function):
+    """q [B*Hq, S, 128], k/v [B*Hkv, S, 128] bf16 contiguous; seq_lens
+    int32 [B] (per batch row, not per head)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, dropout_p, seq_lens, causal, hq, hkv):
+        C = _ops.ext()
+        seed = None
+        if dropout_p > 0:
+            seed = _attn_seed_tensor(q.device)
+            seed.add_(1)
+            seed = seed.clone()
+        o, lse = C.attn_gqa_fwd(q, k, v, float(dropout_p), seed, seq_lens,
+                                bool(causal), hq, hkv)
+        ctx.save_for_backward(q, k, v, o, lse,
+                              seed if seed is not None else
+                              torch.empty(0), seq_lens)
+        ctx.args = (float(dropout_p), bool(causal), hq, hkv)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        C = _ops.ext()
+        q, k, v, o, lse, seed, seq_lens = ctx.saved_tensors
+        p, causal, hq, hkv = ctx.args
+        do = do.contiguous()
+        drow = (do.float() * o.float()).sum(-1)  # [B*Hq, S]
+        dq, dk, dv = C.attn_gqa_bwd(
+            q, k, v, do, lse, drow, p, seed if seed.numel() else None,
+            seq_lens, causal, hq, hkv)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def _flash_attention_gqa(q, k, v, dropout_p, seq_lens, causal):
+    B, h, S, d = q.shape
+    hkv = k.shape[1]
+    if d != 128 or hkv < 1 or h % hkv or k.shape != (B, hkv, S, d) \
+            or v.shape != k.shape:
+        raise ValueError(
+            "grouped-query flash_attention takes q [B,Hq,S,128] and k, v "
+            "[B,Hkv,S,128] with Hkv dividing Hq, got q %s k %s v %s"
+            % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    o = _FlashAttnGqaFn.apply(
+        q.reshape(B * h, S, d).contiguous(),
+        k.reshape(B * hkv, S, d).contiguous(),
+        v.reshape(B * hkv, S, d).contiguous(),
+        dropout_p, seq_lens, causal, h, hkv)
+    return o.view(B, h, S, d)
+
+
+class _FlashAttnGqaPackedFn(torch.autograd.Function):
+    """qkv [B, S, Hq + 2*Hkv, 128] -> O [B, S, Hq*128]; the backward
+    emits the gradient in qkv's layout, which the fused projection's
+    backward consumes as it is."""
+
+    @staticmethod
+    def forward(ctx, qkv, hkv, dropout_p, seq_lens, causal):
+        C = _ops.ext()
+        hq = qkv.shape[2] - 2 * hkv
+        seed = None
+        if dropout_p > 0:
+            seed = _attn_seed_tensor(qkv.device)
+            seed.add_(1)
+            seed = seed.clone()
+        o, lse = C.attn_gqa_fwd_packed(qkv, float(dropout_p), seed,
+                                       seq_lens, bool(causal), hq, hkv)
+        ctx.save_for_backward(qkv, o, lse,
+                              seed if seed is not None else
+                              torch.empty(0), seq_lens)
+        ctx.args = (float(dropout_p), bool(causal), hq, hkv)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        C = _ops.ext()
+        qkv, o, lse, seed, seq_lens = ctx.saved_tensors
+        p, causal, hq, hkv = ctx.args
+        do = do.contiguous()
+        B, S, _ = o.shape
+        # D_i = rowsum(dO o O) per (b,hq,s): [B,S,Hq] -> [B*Hq, S]
+        drow = (do.float() * o.float()).view(B, S, hq, 128).sum(-1) \
+            .transpose(1, 2).reshape(B * hq, S).contiguous()
+        dqkv = C.attn_gqa_bwd_packed(
+            qkv, do, lse, drow, p, seed if seed.numel() else None,
+            seq_lens, causal, hq, hkv)
+        return dqkv, None, None, None, None
+
+
+def flash_attention_gqa_ok(qkv):
+    """Whether a packed ``[B, S, Hq + 2*Hkv, 128]`` buffer can go to
+    flash_attention_gqa_packed."""
+    return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 4
+            and qkv.shape[-1] == 128 and qkv.shape[1] % 64 == 0
+            and qkv.shape[1] > 0)
+
+
+def flash_attention_gqa_packed(qkv, num_kv_heads, dropout_p=0.0,
+                               seq_lens=None, causal=False):
+    """Grouped-query attention over the output of one fused projection:
+    qkv ``[B, S, Hq + 2*Hkv, 128]`` bf16 (heads 0..Hq-1 are Q, then
+    ``num_kv_heads`` = Hkv K heads, then Hkv V heads; Hkv divides Hq)
+    -> O ``[B, S, Hq*128]``. Query head i attends to K/V head
+    ``i // (Hq // Hkv)``. At Hkv == Hq this is the memory layout, and
+    the result, of flash_attention_packed on ``[B,S,3,H,128]``.
+
+    The kernels read the shared K/V heads in place and sum dK/dV over
+    each group in registers, so neither the forward nor the backward
+    holds an Hq-head copy of K, V or their gradients; the sum is rounded
+    to bf16 once. seq_lens (int32 [B]), causal and dropout_p as in
+    flash_attention_packed; with one seed the dropout mask is the one
+    the multi-head kernels draw on K/V expanded to Hq heads."""
+    hkv = int(num_kv_heads)
+    hq = qkv.shape[2] - 2 * hkv if qkv.dim() == 4 else 0
+    if hkv < 1 or hq < 1 or hq % hkv:
+        raise ValueError(
+            "qkv %s is not [B, S, Hq + 2*%d, 128] with %d dividing Hq"
+            % (tuple(qkv.shape), hkv, hkv))
+    return _FlashAttnGqaPackedFn.apply(qkv.contiguous(), hkv, dropout_p,
+                                       seq_lens, causal)
 
 
 # ---------------------------------------------------------------------------
